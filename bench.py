@@ -30,6 +30,14 @@ raises is counted as failed, the run goes on.  Prints ONE JSON line on rank 0.
              BASELINE configs[4] (the 311 scans of datasets/splits/fullscan/scannetv2_test.json) in one command
 --preflight  check the job before anything is built: rank count vs visible devices, a collective all-gather, the NUMA /
              affinity / hardware-queue settings of every rank; one actionable line and a non-zero exit within 60 s
+--full       everything measured or checked after the timed region: the decoder self-check and alone-launch figure, the
+             single-scene latency pass, the per-op rooflines (grouping, FPS, ball query, encoder GEMMs), the stress
+             configuration's f16x1 comparison, the CPU parity sample and the CPU baseline.  Without it a run sets up, warms
+             up, times the steps, writes --dump-outputs and prints the line (`--no-extras`, `--no-latency` and
+             `--no-cpu-baseline` trim a --full run)
+--dump-outputs DIR
+             after the timed region, what the last step returned to its callers as DIR/<name>.npy (float32 / float64):
+             per pass the flat vertex and face buffers of all its meshes and the per-mesh ends (stress: the logits)
 """
 import argparse
 import json
@@ -112,7 +120,15 @@ def parse(argv=None):
     ap.add_argument("--demo-keep", type=int, default=16,
                     help="--config demo: the objectness bias of the seeded head is shifted so that this many of scene "
                          "0's 256 proposals pass the 0.5 threshold (NMS and empty-box removal then thin them out)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need, after the timed region: self-checks, "
+                         "single-scene latency, per-op rooflines, the f16x1 comparison, parity sample and CPU baseline")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, at most 64 MB "
+                         "in all: larger arrays as a fixed seeded sample of their rows)")
     args = ap.parse_args(argv)
+    if not args.full:
+        args.no_extras = args.no_latency = args.no_cpu_baseline = True
     c = CONFIGS[args.config]
     for k in ("points", "resolution0", "upsampling_steps"):
         if getattr(args, k) is None:
@@ -255,6 +271,7 @@ class HipBackend(object):
         self.NB = max(1, args.batch)
         self.record_scenes, self.scene_records = False, []
         self.round_points = {}
+        self.last_out = [None] * self.S            # per worker: (scene ids, [(name, device array)]) of its last pass
         # ONE set of weights / packed weight streams per GPU; every in-flight worker gets a view with its own
         # generator state (round 3 built a full replica per worker)
         self.net = self._build_net()
@@ -364,6 +381,10 @@ class HipBackend(object):
                     ev[3].record()
                     self.scene_records.append({"scenes": [int(i) for i in ids], "worker": w, "events": ev, "queries": 0,
                                                "rounds": 0, "meshes": 0, "vertices": 0, "triangles": 0, "failed": False})
+                empty = torch.zeros(0, 3, dtype=torch.float64, device=self.device)
+                ends = torch.zeros(1, dtype=torch.int32, device=self.device)
+                self.last_out[w] = (ids, [("vertices", empty), ("faces", empty), ("mesh_vertex_end", ends),
+                                          ("mesh_face_end", ends)])
                 return 0, 0, 0, 0
             gen = net.completion.generator
             # the previous scene's PCIe copy rides behind one decode launch (--blit-round; default the first, longest)
@@ -380,7 +401,8 @@ class HipBackend(object):
             meshes = net.reconstruct(end_points, proposal_features, sel, pc,
                                      hook=(lambda codes, cls: ev[2].record()) if ev else None)
             sink.start_pending()          # (dense grid: no rounds; or fewer rounds than --blit-round)
-        v, f, _, _ = gen.last_buffers                              # all K meshes: one vertex / one face buffer
+        v, f, vend, tend = gen.last_buffers                        # all K meshes: one vertex / one face buffer
+        self.last_out[w] = (ids, [("vertices", v), ("faces", f), ("mesh_vertex_end", vend), ("mesh_face_end", tend)])
         sink.push(v, f)
         if self.args.blit_round < 0:
             sink.start_pending()
@@ -395,6 +417,17 @@ class HipBackend(object):
                                        "meshes": len(meshes), "vertices": int(v.shape[0]), "triangles": int(f.shape[0]),
                                        "failed": False})
         return len(meshes), int(v.shape[0]), int(f.shape[0]), gen.stats.get('n_queries', 0)
+
+    def step_outputs(self):
+        """[(name, array)]: what the last pass of every worker returned -- all its meshes as one flat vertex buffer
+        (float64) and one face buffer (int32, indices into the mesh's own vertices), and per-mesh ends into both
+        (mesh k = vertices[vertex_end[k]:vertex_end[k+1]], generator.extract_meshes)"""
+        out = []
+        for rec in self.last_out:
+            if rec is not None:
+                tag = "scene" + "-".join(str(int(i)) for i in rec[0])
+                out += [(tag + "_" + name, a) for name, a in rec[1]]
+        return out
 
     def scene_stats(self):
         """per-scene records of the timed region with the event times resolved (call after the final sync)"""
@@ -446,10 +479,11 @@ class HipBackend(object):
         if on:
             self.scene_records = []
 
-    def final_check(self):
+    def final_check(self, full):
         self._lib.device_status()
-        self.selfcheck = self.decoder_selfcheck(self.dec if hasattr(self, "dec") else self.nets[0].completion.decoder)
-        self.alone = self.decoder_alone()
+        if full:
+            self.selfcheck = self.decoder_selfcheck(self.nets[0].completion.decoder)
+            self.alone = self.decoder_alone()
 
     def decoder_alone(self):
         """After the timed region, nothing else on the GPU: MISE round 0 of one scene (every proposal's level-0 lattice,
@@ -620,14 +654,18 @@ class StressBackend(HipBackend):
     def run_pass(self, w, ids):
         with self.torch.no_grad():
             for _ in ids:
-                self.dec.decode_tiles(self.pts, self.tile_prop, self.table, self.fc_p_w)
+                self.logits = self.dec.decode_tiles(self.pts, self.tile_prop, self.table, self.fc_p_w)
         return self.K * len(ids), 0, 0, self.K * self.T * len(ids)
 
-    def final_check(self):
+    def step_outputs(self):
+        """the occupancy logits of the last decode: 256 proposals x 262 144 points, proposal-major"""
+        return [("logits", self.logits)]
+
+    def final_check(self, full):
         self._lib.device_status()
-        self.selfcheck = self.decoder_selfcheck(self.dec)
-        self.alone = None
-        self.modes = self.compare_modes()
+        if full:
+            self.selfcheck = self.decoder_selfcheck(self.dec)
+            self.modes = self.compare_modes()
 
     def compare_modes(self):
         """configs[2] names "bf16 MFMA MLP": the single-pass 16-bit mode of the same kernel (occ_decode8_kernel<1>: one
@@ -686,6 +724,7 @@ class StubBackend(object):
         self.seen = []
         self.record_scenes, self.scene_records = bool(getattr(args, "stats_out", None)), []
         self.slow = float(os.environ.get("RFD_BENCH_STUB_SLOW_RANK", "-1")) == rank
+        self.last_out = [None] * self.S
 
     def sync(self):
         pass
@@ -701,6 +740,7 @@ class StubBackend(object):
         self.seen += list(ids)
         if self.fail & set(ids):
             raise RuntimeError("stub scene %s failed" % sorted(self.fail & set(ids)))
+        self.last_out[w] = ids
         if self.record_scenes:
             self.scene_records.append({"scenes": [int(i) for i in ids], "worker": w, "failed": False,
                                        "queries": sum(100 + i for i in ids), "ms": {"total": 2.0}})
@@ -716,14 +756,46 @@ class StubBackend(object):
         if on:
             self.scene_records = []
 
-    def final_check(self):
+    def final_check(self, full):
         pass
+
+    def step_outputs(self):
+        import numpy as np
+        return [("scene%s_stub" % "-".join(str(i) for i in ids), np.arange(1000, dtype=np.int32) * (ids[0] + 1))
+                for ids in self.last_out if ids]
 
     def kernel_name(self):
         return "stub"
 
 
 # ------------------------------------------------------------------------ job ---
+DUMP_LIMIT_BYTES = 60 * 10 ** 6          # --dump-outputs: array data of all ranks (under 64 MB with the .npy headers)
+
+
+def dump_outputs(path, arrays, rank=0, world=1):
+    """--dump-outputs: `arrays` [(name, tensor or ndarray)] -> <path>/<name>.npy (rank r > 0: rank<r>_<name>.npy), floats
+    as they are, integers as float64 (exact below 2**53).  Every array gets an equal share of the rank's part of
+    DUMP_LIMIT_BYTES; one larger than its share is written as a sample of its rows -- chosen by a generator seeded with
+    the array's name, so the same for every run and build with the same row count -- and the sorted row indices go
+    beside it as <name>_rows.npy."""
+    import zlib
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    prefix = "rank%d_" % rank if rank else ""
+    share = DUMP_LIMIT_BYTES // max(world, 1) // max(len(arrays), 1)
+    for name, a in arrays:
+        a = torch.as_tensor(a)
+        dtype = a.dtype if a.dtype in (torch.float32, torch.float64) else torch.float64
+        item = torch.empty((), dtype=dtype).element_size()
+        if a.dim() and a.numel() * item > share:
+            k = max(1, share // (item * int(np.prod(a.shape[1:])) + 8))      # + the float64 row index
+            rows = np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(a.shape[0], k, replace=False))
+            np.save(os.path.join(path, prefix + name + "_rows.npy"), rows.astype(np.float64))
+            a = a[torch.from_numpy(rows).to(a.device)]
+        np.save(os.path.join(path, prefix + name + ".npy"), a.to(dtype).cpu().numpy())
+
+
 def run_job(args, be, rank, world, dist):
     """warm-up, barrier, K timed steps, barrier -> per-rank statistics vector."""
     from concurrent.futures import ThreadPoolExecutor
@@ -796,7 +868,9 @@ def run_job(args, be, rank, world, dist):
             json.dump({"rank": rank, "world": world, "config": args.config, "timed_region_s": elapsed,
                        "scenes": be.last_scene_stats}, fh, indent=1)
     be.set_timing(False)
-    be.final_check()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, be.step_outputs(), rank, world)
+    be.final_check(args.full)
     n_meshes, nv, nt, nq = (sum(r[0][i] for r in res) for i in range(4))
     failed = sum(r[1] for r in res)
     n_scenes = sum(len(ids) for p in plan for ids in p)

@@ -11,7 +11,7 @@ Recipe = SURVEY.md Appendix A: bare namespace packages so models/__init__.py
 replaced by the CPU oracle, absent third-party deps stubbed, MISE built from
 the reference's mise.pyx with Cython in a scratch directory.
 
-Usage:  python tests/golden/make_fixtures.py [dec] [mise] [grid] [ops] [net] [net80k] [gen] [nms] [cd] [fit] [mc]
+Usage:  python tests/golden/make_fixtures.py [dec] [mise] [grid] [ops] [net] [net80k] [gen] [nms] [cd] [fit] [mc] [cfg]
 """
 import importlib
 import os
@@ -553,6 +553,13 @@ def make_mc():
         out['bbox_' + k] = npz[k]
     np.savez_compressed(os.path.join(HERE, 'F_MC.npz'), **out)
     print('F_MC.npz', os.path.getsize(os.path.join(HERE, 'F_MC.npz')) // 1024, 'KiB', names)
+
+
+def make_cfg():
+    """ISCNet_test.yaml: the reference's test-time config file (configs/config_files/ISCNet_test.yaml), byte for byte;
+    tests/test_modules_cpu.py checks that Config.from_yaml reads it and that the defaults are its values"""
+    import shutil
+    shutil.copyfile(REF + '/configs/config_files/ISCNet_test.yaml', os.path.join(HERE, 'ISCNet_test.yaml'))
 
 
 if __name__ == "__main__":

@@ -288,3 +288,43 @@ def test_scenes_flag_sweeps_the_311_scan_split_over_eight_ranks(tmp_path):
         assert ids == [first + j for j in range(r, 311, 8)], r
         seen += ids
     assert sorted(seen) == list(range(first, first + 311))
+
+
+def test_dump_outputs_of_the_last_step_and_the_lean_default(tmp_path):
+    """`--dump-outputs DIR` writes what the last timed step returned, rank 0 as <name>.npy and rank r as rank<r>_<name>.npy,
+    as float arrays; the same command writes the same files.  Without --full nothing is measured after the timed region."""
+    import numpy as np
+    for d in ("a", "b"):
+        p = run_bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--in-flight", "2", "--dump-outputs", str(tmp_path / d)])
+        assert p.returncode == 0, p.stderr
+        out = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][0])
+        assert out["steps"] == 2 and out["ms_per_step"] > 0 and "single_scene" not in out and "cpu_baseline" not in out
+    # scenes 0-3 warm up, 4-7 and 8-11 are the two timed steps: the last one's scenes, split over 2 ranks x 2 workers
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["rank1_scene11_stub.npy", "rank1_scene9_stub.npy", "scene10_stub.npy", "scene8_stub.npy"]
+    for n in names:
+        a = np.load(tmp_path / "a" / n)
+        assert a.dtype == np.float64 and np.array_equal(a, np.load(tmp_path / "b" / n))
+
+
+def test_dump_outputs_samples_what_does_not_fit(tmp_path):
+    """64 MB in all: an array larger than its share is written as a seeded sample of its rows plus the row indices"""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    big = torch.arange(3 * 10 ** 7, dtype=torch.int32).reshape(-1, 3)
+    logits = torch.linspace(-1, 1, 2 * 10 ** 7)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), [("faces", big), ("logits", logits), ("ends", [0, 5, 9])])
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["ends.npy", "faces.npy", "faces_rows.npy", "logits.npy", "logits_rows.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / n) for n in names) <= 64 * 10 ** 6
+    for name, full in (("faces", big.numpy()), ("logits", logits.numpy())):
+        rows = np.load(tmp_path / "a" / (name + "_rows.npy"))
+        got = np.load(tmp_path / "a" / (name + ".npy"))
+        assert rows.dtype == np.float64 and np.all(np.diff(rows) > 0) and len(rows) > 10 ** 5
+        assert got.dtype == (np.float64 if name == "faces" else np.float32)
+        assert np.array_equal(got, full[rows.astype(np.int64)])
+        assert np.array_equal(rows, np.load(tmp_path / "b" / (name + "_rows.npy")))
+    assert np.array_equal(np.load(tmp_path / "a" / "ends.npy"), [0.0, 5.0, 9.0])

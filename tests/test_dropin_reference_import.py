@@ -1,4 +1,4 @@
-"""CPU, dev container only (skipped where /root/reference is absent, e.g. on the GPU box): the drop-in boundary
+"""CPU; every test but the foreign-package one needs a reference checkout and is skipped without it: the drop-in boundary
 exercised through the REFERENCE's own import chain, not by file path.
 
 The reference reaches its op package under two names:
@@ -19,7 +19,7 @@ import pytest
 
 REF = "/root/reference"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="reference checkout not present")
+needs_ref = pytest.mark.skipif(not os.path.isdir(REF), reason="reference checkout not present")
 
 # bare namespace packages for `models*`, so that models/__init__.py (-> loss.py -> Chamfer JIT
 # build + .cuda()) is never executed
@@ -96,6 +96,7 @@ REF_OPS = os.path.join(REF, "external", "pointnet2_ops_lib", "pointnet2_ops")
 OUR_OPS = os.path.join(ROOT, "rfdnet_amd", "pointnet2_ops")
 
 
+@needs_ref
 def test_reference_python_on_our_ext_without_install():
     """reference checkout AHEAD of this repository: the reference's own pointnet2_utils / pointnet2_modules run,
     on top of our `pointnet2_ops._ext`; nothing is installed or patched"""
@@ -103,6 +104,7 @@ def test_reference_python_on_our_ext_without_install():
     assert "BOUND " + REF_OPS in out
 
 
+@needs_ref
 def test_overlay_without_install():
     """this repository AHEAD of the reference: `external.pointnet2_ops_lib.pointnet2_ops` is our overlay (fused module
     classes), the rest of the reference's `external` namespace still resolves to the reference"""
@@ -115,6 +117,7 @@ assert spec is not None and spec.origin.startswith(REF), spec
     assert "BOUND " + OUR_OPS in out
 
 
+@needs_ref
 def test_install_default_keeps_reference_python():
     """`dropin.install()` with only the reference on the path: appends this repository, reference Python on our _ext"""
     body = ("sys.path.insert(0, ROOT)\nfrom rfdnet_amd import dropin\nsys.path.remove(ROOT)\n"
@@ -124,6 +127,7 @@ def test_install_default_keeps_reference_python():
     run(body, [REF])
 
 
+@needs_ref
 def test_install_overlay_after_reference_namespace_was_imported():
     """`dropin.install(overlay=True)` also works late: after something already imported the reference's `external`
     namespace, the overlay still takes over `external.pointnet2_ops_lib.pointnet2_ops`"""
@@ -147,6 +151,7 @@ def test_foreign_pointnet2_ops_is_reported(tmp_path):
     run(body, [str(tmp_path), ROOT])
 
 
+@needs_ref
 def test_wheel_provides_both_identities(tmp_path):
     """what `pip install .` lays down (a wheel built from setup.py, unpacked -- site-packages is never touched):
     both identities importable from the unpacked tree alone, reference Python binds to its _ext"""

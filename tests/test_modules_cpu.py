@@ -123,7 +123,8 @@ def test_mean_size_array_sources(tmp_path, monkeypatch):
     assert np.array_equal(c.mean_size_arr, arr + 1) and not c.placeholder_sizes
 
 
-REF_YAML = "/root/reference/configs/config_files/ISCNet_test.yaml"
+# the reference's configs/config_files/ISCNet_test.yaml, stored as a fixture (tests/golden/make_fixtures.py cfg)
+REF_YAML = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ISCNet_test.yaml")
 
 
 def test_config_from_a_reference_style_yaml(tmp_path):
@@ -166,7 +167,6 @@ log: {vis_path: visualization, path: out/iscnet}
     assert cfg2.config["mode"] == "test" and cfg2.config["generation"]["upsampling_steps"] == 0
 
 
-@pytest.mark.skipif(not os.path.exists(REF_YAML), reason="reference checkout not present")
 def test_the_reference_config_file_itself_loads():
     from rfdnet_amd.iscnet.config import Config, DEFAULT_CONFIG
     cfg = Config.from_yaml(REF_YAML, mode="demo")
