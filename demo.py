@@ -5,6 +5,7 @@ write the reference's output files.
 
   python demo.py --demo_path demo/inputs/scene0549_00.off --out out/scene0549_00
   python demo.py --synthetic 10 --out out/synth --upsampling_steps 1
+  python demo.py --synthetic 10 --out out/synth --with_normals     (PLYs with per-vertex nx ny nz)
 
 Weights: --weight <pretrained_weight.pth> (reference checkpoint, key names kept);
 without it seeded random weights are used (no pretrained weights ship with the
@@ -16,7 +17,7 @@ import numpy as np
 import torch
 
 
-def main():
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", type=str, default=None,
                     help="a reference config file (configs/config_files/ISCNet_test.yaml); its data / model / test / "
@@ -36,7 +37,14 @@ def main():
                     help="synthetic runs only: let --selection nms decode boxes with placeholder class mean sizes when "
                          "no scannet_means.npz is available (the reference fails hard on the missing file; so does this "
                          "path without the flag)")
-    args = ap.parse_args()
+    ap.add_argument("--with_normals", action="store_true",
+                    help="vertex normals from the occupancy field's gradient (generation.with_normals, "
+                         "Generator3D.estimate_normals), written to the mesh PLYs as nx ny nz")
+    return ap
+
+
+def main():
+    args = build_parser().parse_args()
 
     from rfdnet_amd import io, synthetic
     from rfdnet_amd.iscnet.config import Config
@@ -44,6 +52,8 @@ def main():
 
     gen = {k: v for k, v in (('resolution_0', args.resolution_0), ('upsampling_steps', args.upsampling_steps))
            if v is not None}
+    if args.with_normals:
+        gen['with_normals'] = True
     if args.config:
         cfg = Config.from_yaml(args.config, mode=args.mode, overrides={'generation': gen},
                                mean_size_arr=args.mean_size_npz)

@@ -240,6 +240,30 @@ int rfd_occ_set_tail_tiles(int n_tiles);
 int rfd_occ_chunk_range_capped(int k, int n_tiles, int n_workgroups, int max_chunk, int *begin, int *end,
                                int *n_chunks);
 
+/* ---- vertex normals from the decoder's input gradient (csrc/occ_normals.hip) ---------------------------------------
+ * Generator3D.estimate_normals (generator.py:200-224): for every vertex p of mesh k, g = d logit_k(p) / d p (reverse mode
+ * through the fused decoder: forward pass keeping the ReLU masks only, backward pass on the matrix cores) and
+ * normals = -g / |g|, all K meshes in one launch.
+ *  n_groups   sum over meshes of ceil(vertices / 16)
+ *  verts      [V][3] f64 vertices of all meshes back to back (the rfd_mc_emit_affine buffer); rounded to f32 on load
+ *  vend       [K+1] int32 vertex offsets: mesh k = vertices vend[k] .. vend[k+1]-1
+ *  gprefix    [K+1] int32 group offsets: gprefix[k] = sum_{k'<k} ceil((vend[k'+1]-vend[k']) / 16), gprefix[K] = n_groups
+ *  packed_fwd the decoder's stream (rfd_occ_pack_weights_w8(fc_0, fc_1, kw0, kw1))
+ *  packed_bwd rfd_occ_pack_weights_w8(fc0' = blocks[4-j].fc_1.weight^T, fc1' = blocks[4-j].fc_0.weight^T, kb0, kb1):
+ *             the transposed matrices in reverse block order, a buffer of rfd_occ_packed_bytes() bytes
+ *  kw         HOST int[12]: kw0[0..4], kw1, kb0[0..4], kb1
+ *  fc_p_w, table, fc_out_w  as for rfd_occ_decode_w8 (the table and fc_p_w of the same fold)
+ *  normals    [V][3] f32 out: -g / |g|; a vertex whose gradient is exactly zero gets 0/0 = NaN (what the reference's
+ *             ni / torch.norm(ni) gives)
+ *  grad       [V][3] f32 out (or NULL): g itself
+ *  mode       RFD_OCC_MODE_F16X3 only (anything else: hipErrorInvalidValue)
+ * Status bit 2 (the stream's status word): an activation of the forward pass, or a back-propagated value, beyond the f16
+ * range at the table's scale -- the same flag and the same answer (refold at the fallback scale) as the decoder. */
+int rfd_occ_normals_w8(int n_groups, const double *verts, const int *vend, const int *gprefix, int K,
+                       const void *packed_fwd, const void *packed_bwd, const int *kw, const float *fc_p_w,
+                       const float *table, const float *fc_out_w, float *normals, float *grad, int mode,
+                       void *stream);
+
 /* ---- fp32-class GEMM on the f16 matrix cores (csrc/gemm_f16x3.hip) -----------------
  * C[M,N] = act(A)[M,K] . W[N,K]^T (+ bias[N]) (+ gbias[m / rows_per_group][N]) (+ R[M,N]),
  * optional ReLU on A and on C; three f16 MFMAs per product on (hi, lo) operand splits.

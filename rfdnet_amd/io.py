@@ -84,12 +84,19 @@ def load_demo_data(points_or_path, num_point=80000, no_height=False, seed=10):
     return {'point_clouds': torch.from_numpy(pc.astype(np.float32)[None])}
 
 
-def write_mesh_ply(path, vertices, faces):
+def write_mesh_ply(path, vertices, faces, normals=None):
+    """Binary PLY of a triangle mesh; normals (V,3): per-vertex `nx ny nz` after x y z (trimesh's vertex-normal layout).
+    Without normals the file is the plain x y z one."""
     v = np.asarray(vertices, dtype=np.float32)
     f = np.asarray(faces, dtype=np.int32)
+    props = "property float x\nproperty float y\nproperty float z\n"
+    if normals is not None:
+        n = np.asarray(normals, dtype=np.float32).reshape(v.shape[0], 3)
+        props += "property float nx\nproperty float ny\nproperty float nz\n"
+        v = np.concatenate([v.reshape(-1, 3), n], axis=1)
     header = ("ply\nformat binary_little_endian 1.0\ncomment rfdnet_amd\nelement vertex %d\n"
-              "property float x\nproperty float y\nproperty float z\nelement face %d\n"
-              "property list uchar int vertex_indices\nend_header\n" % (v.shape[0], f.shape[0]))
+              "%selement face %d\n"
+              "property list uchar int vertex_indices\nend_header\n" % (v.shape[0], props, f.shape[0]))
     rec = np.empty(f.shape[0], dtype=[('n', 'u1'), ('i', '<i4', (3,))])
     rec['n'] = 3
     rec['i'] = f
@@ -99,16 +106,22 @@ def write_mesh_ply(path, vertices, faces):
         fh.write(rec.tobytes())
 
 
-def read_mesh_ply(path):
+def read_mesh_ply(path, return_normals=False):
+    """-> vertices (V,3), faces (F,3) [, normals (V,3) or None when the file has none]"""
     with open(path, "rb") as fh:
         data = fh.read()
     end = data.index(b"end_header\n") + len(b"end_header\n")
     head = data[:end].decode("ascii").split("\n")
     nv = int([l for l in head if l.startswith("element vertex")][0].split()[-1])
     nf = int([l for l in head if l.startswith("element face")][0].split()[-1])
-    v = np.frombuffer(data, dtype='<f4', count=nv * 3, offset=end).reshape(nv, 3)
-    rec = np.frombuffer(data, dtype=[('n', 'u1'), ('i', '<i4', (3,))], count=nf, offset=end + nv * 12)
-    return v.copy(), rec['i'].copy()
+    has_n = "property float nx" in head
+    w = 6 if has_n else 3
+    vn = np.frombuffer(data, dtype='<f4', count=nv * w, offset=end).reshape(nv, w)
+    rec = np.frombuffer(data, dtype=[('n', 'u1'), ('i', '<i4', (3,))], count=nf, offset=end + nv * 4 * w)
+    v, f = vn[:, :3].copy(), rec['i'].copy()
+    if return_normals:
+        return v, f, (vn[:, 3:].copy() if has_n else None)
+    return v, f
 
 
 def write_points_ply(path, points):
@@ -129,7 +142,10 @@ def save_visualization(output_dir, point_clouds, proposal_ids, meshes, box_param
     for mesh, pid in zip(meshes, ids[:, 0]):
         v = mesh.vertices.cpu().numpy() if hasattr(mesh.vertices, "cpu") else mesh.vertices
         f = mesh.faces.cpu().numpy() if hasattr(mesh.faces, "cpu") else mesh.faces
-        write_mesh_ply(os.path.join(output_dir, 'proposal_%d_mesh.ply' % int(pid)), v, f)
+        n = getattr(mesh, "vertex_normals", None)
+        if n is not None and hasattr(n, "cpu"):
+            n = n.cpu().numpy()
+        write_mesh_ply(os.path.join(output_dir, 'proposal_%d_mesh.ply' % int(pid)), v, f, n)
     write_points_ply(os.path.join(output_dir, '%06d_pc.ply' % batch_id), np.asarray(point_clouds)[batch_id])
     if box_params is not None:
         bp = np.asarray(box_params, dtype=np.float64)

@@ -40,10 +40,9 @@ class Generator3D(object):
                  resolution0=16, upsampling_steps=3, with_normals=False, padding=0.1,
                  sample=False, use_cls_for_completion=False, simplify_nfaces=None,
                  preprocessor=None):
-        if refinement_step or with_normals or simplify_nfaces is not None:
-            # disabled by ISCNet_test.yaml:64-66; refine_mesh / estimate_normals /
-            # libsimplify are out of scope
-            raise NotImplementedError("refinement / normals / simplification are not on the hot path")
+        if refinement_step or simplify_nfaces is not None:
+            # disabled by ISCNet_test.yaml:64-66; refine_mesh / libsimplify are out of scope
+            raise NotImplementedError("refinement / simplification are not on the hot path")
         self.model = model
         self.round_hook = None
         self.points_batch_size = points_batch_size      # kept for signature parity; no chunking needed
@@ -61,16 +60,20 @@ class Generator3D(object):
         # dirty slabs only (identical result; 0 = never)
         self.sparse_round_points = int(os.environ.get('RFD_MISE_SPARSE_POINTS', 1024))     # (the variable: A/B runs only)
         self.stats = {}
+        self.last_normals = None        # with_normals: the (V,3) f32 normals of the last extract_meshes(), all meshes
 
     # ---- reference-shaped entry points ------------------------------------------
     def generate_mesh(self, object_features, cls_codes, return_stats=True):
-        """object_features (K, c_dim) -> list of K meshes (generator.py:54-76)."""
-        grids = self.generate_grids(object_features, cls_codes)
-        return self.extract_meshes(grids)
+        """object_features (K, c_dim) -> list of K meshes (generator.py:54-76).  with_normals: every mesh's
+        vertex_normals (generator.py:173-176), all K meshes in one launch after marching cubes."""
+        fold = []
+        grids = self.generate_grids(object_features, cls_codes, fold_out=fold)
+        return self.extract_meshes(grids, fold=fold[0] if self.with_normals else None)
 
     def generate_from_latent(self, z, c=None, device='cuda', **kwargs):
-        grids = self._grids(z, c)
-        return self.extract_meshes(grids)[0]
+        fold = []
+        grids = self._grids(z, c, fold_out=fold)
+        return self.extract_meshes(grids, fold=fold[0] if self.with_normals else None)[0]
 
     def eval_points(self, p, z, c=None, device='cuda', **kwargs):
         """p (T,3) -> logits (T,) for one code (generator.py:123-143)."""
@@ -81,7 +84,7 @@ class Generator3D(object):
     def logit_threshold(self):
         return float(np.log(self.threshold) - np.log(1. - self.threshold))   # generator.py:85
 
-    def generate_grids(self, object_features, cls_codes=None):
+    def generate_grids(self, object_features, cls_codes=None, fold_out=None):
         """-> value grids (K, n, n, n) float32 on the device; n = resolution0 for
         the dense path, (resolution0 << upsampling_steps) + 1 for MISE."""
         self.model.eval()
@@ -89,15 +92,19 @@ class Generator3D(object):
             object_features = torch.cat([object_features, cls_codes], dim=-1)
         K = object_features.size(0)
         z = self.model.get_z_from_prior((K,), sample=self.sample, device=object_features.device)
-        return self._grids(z, object_features)
+        return self._grids(z, object_features, fold_out=fold_out)
 
     @torch.no_grad()
-    def _grids(self, z, c):
+    def _grids(self, z, c, fold_out=None):
+        """fold_out (a list): receives the (table, fc_p_w) this call folded -- passed along by argument, not kept in an
+        attribute (worker_view() copies the generator per host thread)"""
         dec = self.model.decoder
         dev = c.device
         K = c.size(0)
         box_size = 1 + self.padding                                         # generator.py:88
         table, fc_p_w = dec.fold(z.float(), c.float())
+        if fold_out is not None:
+            fold_out.append((table, fc_p_w))
         if self.upsampling_steps == 0:                                      # :91-97 dense shortcut
             nx = self.resolution0
             total = nx ** 3
@@ -213,7 +220,9 @@ class Generator3D(object):
         return c[1]
 
     # ---- mesh extraction ------------------------------------------------------------
-    def extract_meshes(self, grids):
+    def extract_meshes(self, grids, fold=None):
+        """fold = (table, fc_p_w) of the codes the grids came from: vertex normals from the decoder's gradient
+        (Generator3D.estimate_normals), one launch for all meshes"""
         from .mcubes import marching_cubes_batch
         thr = self.logit_threshold()
         n = grids.shape[1]
@@ -228,7 +237,36 @@ class Generator3D(object):
         v, f, vend, tend = marching_cubes_batch(grids, thr, pad_value=-1e6, return_flat=True,
                                                 affine=(a, -1.5 * a - 0.5 * box_size))
         self.last_buffers = (v, f, vend, tend)
-        return [Mesh(v[vend[k]:vend[k + 1]], f[tend[k]:tend[k + 1]]) for k in range(len(vend) - 1)]
+        self.last_normals = None
+        if fold is None:
+            return [Mesh(v[vend[k]:vend[k + 1]], f[tend[k]:tend[k + 1]]) for k in range(len(vend) - 1)]
+        # generator.py:173-176: normals of every non-empty mesh; the reference leaves them None on an empty one
+        nrm = self.last_normals = self.model.decoder.normals(v, vend, fold[0], fold[1])
+        return [Mesh(v[vend[k]:vend[k + 1]], f[tend[k]:tend[k + 1]],
+                     nrm[vend[k]:vend[k + 1]] if vend[k + 1] > vend[k] else None) for k in range(len(vend) - 1)]
+
+    def estimate_normals(self, vertices, z, c=None, device='cuda'):
+        """generator.py:200-224: vertices (V,3) numpy (rounded to fp32 like torch.FloatTensor), one code z (Z,), c (C,)
+        -> numpy (V,3) f32 normals -g / |g| of the decoder's logit (NaN where the gradient is exactly zero)."""
+        dec = self.model.decoder
+        dev = c.device if c is not None and c.is_cuda else torch.device(device)
+        v = torch.as_tensor(np.ascontiguousarray(vertices, dtype=np.float64)).to(dev)
+        with torch.no_grad():
+            table, fc_p_w = dec.fold(z.reshape(1, -1).float().to(dev), c.reshape(1, -1).float().to(dev))
+            ka_used = dec.ka
+            nrm = dec.normals(v, [0, v.shape[0]], table, fc_p_w)
+            with torch.cuda.device(dev):
+                st = _lib.stream_status_bits()
+            if st & 2:
+                with _lib.BUILD_LOCK:
+                    lowered = dec.lower_activation_scale()
+                if lowered or dec.ka < ka_used:
+                    table, fc_p_w = dec.fold(z.reshape(1, -1).float().to(dev), c.reshape(1, -1).float().to(dev))
+                    nrm = dec.normals(v, [0, v.shape[0]], table, fc_p_w)
+                    with torch.cuda.device(dev):
+                        st = (st & ~2) | _lib.stream_status_bits()
+            _lib.raise_status(st)
+        return nrm.cpu().numpy()
 
     def extract_mesh(self, occ_hat, z=None, c=None):
         g = torch.as_tensor(occ_hat, dtype=torch.float32)

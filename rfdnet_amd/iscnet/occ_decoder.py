@@ -125,6 +125,98 @@ class DecoderCBatchNorm(nn.Module):
             self._packed = (packed, kw0, kw1, key)      # one tuple, one store: readers never see a half-updated pair
         return self._packed[:3]
 
+    def packed_weights_bwd(self):
+        """The weight stream of the normals kernel's backward pass (csrc/occ_normals.hip): rfd_occ_pack_weights_w8 of
+        fc0' = blocks[4-j].fc_1.weight^T and fc1' = blocks[4-j].fc_0.weight^T.  Cached under packed_weights()'s key.
+        Returns (packed, kb0, kb1)."""
+        key = self._weights_key() + (self.kernel,)
+        hit = getattr(self, "_packed_bwd", None)
+        if hit is not None and hit[3] == key:
+            return hit[:3]
+        with _lib.BUILD_LOCK:
+            hit = getattr(self, "_packed_bwd", None)
+            if hit is not None and hit[3] == key:
+                return hit[:3]
+            sd = {k: v.detach() for k, v in self.state_dict().items()}
+            fc0, fc1 = occ_fold.stacked_fc_weights(sd)
+            if not fc0.is_cuda:
+                raise RuntimeError("CPU not supported")
+            b0 = fc1.flip(0).transpose(1, 2).contiguous()          # W1^T of blocks 4 .. 0
+            b1 = fc0.flip(0).transpose(1, 2).contiguous()          # W0^T of blocks 4 .. 0
+            kb0 = [occ_fold.choose_kw([b0[j]]) for j in range(5)]
+            kb1 = occ_fold.choose_kw([b1])
+            packed = torch.empty(_lib.lib().rfd_occ_packed_bytes(), dtype=torch.uint8, device=fc0.device)
+            arr = (C.c_int * 5)(*kb0)
+            with torch.cuda.device(fc0.device):
+                rc = _lib.lib().rfd_occ_pack_weights_w8(b0.data_ptr(), b1.data_ptr(), arr, kb1, packed.data_ptr(),
+                                                        _lib.current_stream())
+            _lib.check(rc, "rfd_occ_pack_weights_w8")
+            _lib.publish(fc0.device)
+            self._packed_bwd = (packed, kb0, kb1, key)
+        return self._packed_bwd[:3]
+
+    def normals(self, verts, vend, table, fc_p_w, return_grad=False):
+        """Vertex normals -g / |g|, g = d logit / d p, of K meshes in one launch (csrc/occ_normals.hip;
+        Generator3D.estimate_normals, generator.py:200-224).
+        verts (V,3) f64 device tensor (all meshes back to back), vend: K + 1 vertex offsets (list or sequence), table /
+        fc_p_w: the fold of the meshes' codes (fold()).  -> normals (V,3) f32 [, grad (V,3) f32].  A vertex whose gradient
+        is exactly zero gets NaN (0/0, as in the reference).  Asynchronous: the f16-range flag (status bit 2) is left in
+        the stream's status word for the caller to read, like decode_tiles()."""
+        if self.mode != MODE_F16X3:
+            raise NotImplementedError("vertex normals need the parity mode (MODE_F16X3); MODE_F16X1 is not supported")
+        if self.kernel != "w8":
+            raise NotImplementedError("vertex normals use the eight-wave decoder's weight stream (kernel 'w8')")
+        assert verts.is_cuda and verts.dtype == torch.float64 and verts.is_contiguous() and verts.dim() == 2
+        assert table.is_contiguous() and table.dtype == torch.float32 and fc_p_w.is_contiguous()
+        vend = [int(x) for x in vend]
+        K = len(vend) - 1
+        assert K >= 1 and vend[0] == 0 and vend[-1] <= verts.shape[0] and table.shape[0] >= K
+        counts = [vend[k + 1] - vend[k] for k in range(K)]
+        gprefix = [0]
+        for n in counts:
+            gprefix.append(gprefix[-1] + (n + 15) // 16)
+        V = vend[-1]
+        dev = verts.device
+        normals = torch.empty(V, 3, dtype=torch.float32, device=dev)
+        grad = torch.empty(V, 3, dtype=torch.float32, device=dev) if return_grad else None
+        if gprefix[-1]:
+            packed, kw0, kw1 = self.packed_weights()
+            packed_b, kb0, kb1 = self.packed_weights_bwd()
+            bounds = torch.tensor([vend, gprefix], dtype=torch.int32).to(dev, non_blocking=True)
+            wo = self.fc_out.weight.detach().reshape(-1).contiguous()
+            kw = (C.c_int * 12)(*(list(kw0) + [kw1] + list(kb0) + [kb1]))
+            with torch.cuda.device(dev):
+                rc = _lib.lib().rfd_occ_normals_w8(
+                    gprefix[-1], verts.data_ptr(), bounds[0].data_ptr(), bounds[1].data_ptr(), K, packed.data_ptr(),
+                    packed_b.data_ptr(), kw, fc_p_w.data_ptr(), table.data_ptr(), wo.data_ptr(), normals.data_ptr(),
+                    grad.data_ptr() if grad is not None else None, self.mode, _lib.current_stream())
+            _lib.check(rc, "rfd_occ_normals_w8")
+        return (normals, grad) if return_grad else normals
+
+    def input_grad(self, p, z, c):
+        """d logit / d p of forward(p, z, c) (p (B,T,3)) -> (B,T,3) f32, with the f16-range flag answered like forward()'s."""
+        B, T, _ = p.shape
+        if c.dim() == 3:
+            c = c.squeeze(2)
+        verts = p.detach().reshape(-1, 3).double().contiguous()
+        vend = [b * T for b in range(B + 1)]
+        ka_used = self.ka
+        table, fc_p_w = self.fold(z.detach().float(), c.detach().float())
+        _, grad = self.normals(verts, vend, table, fc_p_w, return_grad=True)
+        if self.check_range:
+            with torch.cuda.device(p.device):
+                st = _lib.stream_status_bits()
+            if st & 2:
+                with _lib.BUILD_LOCK:
+                    lowered = self.lower_activation_scale()
+                if lowered or self.ka < ka_used:
+                    table, fc_p_w = self.fold(z.detach().float(), c.detach().float())
+                    _, grad = self.normals(verts, vend, table, fc_p_w, return_grad=True)
+                    with torch.cuda.device(p.device):
+                        st = (st & ~2) | _lib.stream_status_bits()
+            _lib.raise_status(st)
+        return grad.view(B, T, 3)
+
     def _fc_out_bias(self):
         b = self.fc_out.bias
         key = (b.data_ptr(), b._version)
@@ -207,9 +299,19 @@ class DecoderCBatchNorm(nn.Module):
         return logits
 
     def forward(self, p, z, c, **kwargs):
-        """p (B,T,3), z (B,Z), c (B,C) -> logits (B,T).  occ_decoder.py:110-123."""
+        """p (B,T,3), z (B,Z), c (B,C) -> logits (B,T).  occ_decoder.py:110-123.
+
+        Gradients: when p requires grad (and grad mode is on) the logits carry a grad_fn whose backward gives
+        dL/dp = dL/dlogit * d logit / d p through the normals kernel (csrc/occ_normals.hip) -- what the reference's
+        Generator3D.estimate_normals needs (vi.requires_grad_(); decode(vi).logits.sum().backward(); -vi.grad).  That is
+        the ONLY gradient this module has: none for z, c (an error if either requires grad) and none for the parameters."""
         if not p.is_cuda:
             raise RuntimeError("CPU not supported")
+        if torch.is_grad_enabled() and p.requires_grad:
+            if z.requires_grad or c.requires_grad:
+                raise NotImplementedError("DecoderCBatchNorm: only the gradient with respect to the query points p is "
+                                          "implemented (not z or c)")
+            return _DecodeWithInputGrad.apply(p, z, c, self)
         B, T, _ = p.shape
         if c.dim() == 3:
             c = c.squeeze(2)
@@ -239,3 +341,20 @@ class DecoderCBatchNorm(nn.Module):
                     st = (st & ~2) | _lib.stream_status_bits()
             _lib.raise_status(st)
         return logits.view(B, tpad)[:, :T]
+
+
+class _DecodeWithInputGrad(torch.autograd.Function):
+    """logits = decoder(p, z, c) with backward dL/dp = dL/dlogits * d logit / d p (normals kernel); no other gradient."""
+
+    @staticmethod
+    def forward(ctx, p, z, c, dec):
+        ctx.dec = dec
+        ctx.save_for_backward(p, z, c)
+        with torch.no_grad():
+            return dec(p.detach(), z.detach(), c.detach())
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        p, z, c = ctx.saved_tensors
+        g = ctx.dec.input_grad(p, z, c)
+        return (grad_out.to(g.dtype).unsqueeze(-1) * g).to(p.dtype), None, None, None

@@ -32,6 +32,7 @@ class ONet(nn.Module):
                 self, threshold=data['threshold'], resolution0=gen['resolution_0'],
                 upsampling_steps=gen['upsampling_steps'], sample=gen['use_sampling'],
                 refinement_step=gen['refinement_step'], simplify_nfaces=gen['simplify_nfaces'],
+                with_normals=gen.get('with_normals', False),
                 preprocessor=None)
 
     def get_prior_z(self, z_dim, device):
