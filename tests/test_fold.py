@@ -135,3 +135,74 @@ def test_folded_layers_are_built_once_when_several_host_threads_share_a_network(
     assert all(o[0] is out[0][0] and o[1] is out[0][1] for o in out)
     ref = conv.weight[:, :, 0] * (bn.weight / torch.sqrt(bn.running_var + bn.eps))[:, None]
     assert torch.allclose(out[0][0], ref.detach(), atol=1e-6)
+
+
+# ------------------------------------------------------------ per-layer weight exponents that differ ----
+def _spread_setup(golden_dir, n_pts=512):
+    """F_DEC's codes and points on tests/weight_scales.py's decoder: five distinct kw0, kw1 none of them"""
+    from weight_scales import spread_decoder
+    fx, sd = _setup(golden_dir)
+    p = fx["p"][:, :n_pts]
+    sd_np, kw0, kw1, kb0, kb1 = spread_decoder(sd, p=p, z=fx["z"], c=fx["c"])
+    return fx, p, {k: torch.from_numpy(v) for k, v in sd_np.items()}, sd_np, kw0, kw1
+
+
+def _emulated_error(fx, p, sd, sd_np, table_kw0, table_kw1, split_kw0, split_kw1):
+    """max |emulated kernel - float64| over F_DEC's three codes: the table folded with one set of exponents, the
+    weights split with another (equal sets: what the kernel computes)"""
+    from dec_f64 import decoder_f64
+    fc0, fc1 = occ_fold.stacked_fc_weights(sd)
+    table, fc_p_w = occ_fold.fold_table(sd, torch.from_numpy(fx["z"]), torch.from_numpy(fx["c"]), table_kw0, table_kw1)
+    exact = decoder_f64(sd_np, p, fx["z"], fx["c"])
+    wout = sd["fc_out.weight"].reshape(-1).numpy()
+    bout = float(sd["fc_out.bias"])
+    err = 0.0
+    with np.errstate(all="ignore"):
+        for k in range(p.shape[0]):
+            out = emulate(table[k].numpy(), fc_p_w.numpy(), fc0.numpy(), fc1.numpy(), split_kw0, split_kw1,
+                          wout, bout, p[k])
+            e = np.abs(out.astype(np.float64) - exact[k]).max()
+            err = max(err, e if np.isfinite(e) else np.inf)
+    return err
+
+
+def test_fold_plus_split_emulation_with_distinct_weight_exponents(golden_dir):
+    """tests/weight_scales.py's decoder (kw0 = five different values, kw1 none of them; the premise is asserted there):
+    the host fold + the kernel's split arithmetic still reproduce the float64 module, 3 codes x 512 points"""
+    fx, p, sd, sd_np, kw0, kw1 = _spread_setup(golden_dir)
+    assert len(set(kw0)) == 5 and kw1 not in kw0
+    err = _emulated_error(fx, p, sd, sd_np, kw0, kw1, kw0, kw1)
+    print("distinct exponents kw0 %s kw1 %d: max |emulated - f64| = %.2e" % (kw0, kw1, err))
+    assert err < 2e-5, err
+
+
+def test_stacked_fold_equals_layerwise_fold_with_distinct_weight_exponents(golden_dir):
+    fx, p, sd, sd_np, kw0, kw1 = _spread_setup(golden_dir)
+    z, c = torch.from_numpy(fx["z"]), torch.from_numpy(fx["c"])
+    t_ref, w_ref = occ_fold.fold_table(sd, z, c, kw0, kw1)
+    t, w = occ_fold.fold_table_stacked(occ_fold.stacked_constants(sd, kw0, kw1), z, c)
+    assert torch.equal(w, w_ref)
+    assert torch.allclose(t, t_ref, rtol=1e-5, atol=1e-5 * float(t_ref.abs().max()))
+    # the rows' scales differ by 2^kw0[i] (and row 0 by 2^(ka+kw1)): the same bound, row by row
+    for r in range(occ_fold.TABLE_ROWS):
+        assert torch.allclose(t[:, r], t_ref[:, r], rtol=1e-5, atol=1e-5 * float(t_ref[:, r].abs().max())), r
+
+
+def test_mixed_up_weight_exponents_are_caught_by_the_emulation(golden_dir):
+    """Negative control of the two tests above: with the exponents the kernel would see mixed up -- kw0 permuted or
+    reversed in the weight split, kw1 replaced by kw0[0], or the fold's S1 rows all undoing kw0[0] -- the same
+    emulation is far from float64 (non-finite or > 1e-2).  If a change flattened the exponents again, these would pass
+    with the correct ones and fail here."""
+    fx, p, sd, sd_np, kw0, kw1 = _spread_setup(golden_dir, n_pts=256)
+    wrong = {
+        "split: kw0 rotated": (kw0, kw1, kw0[1:] + kw0[:1], kw1),
+        "split: kw0 reversed": (kw0, kw1, kw0[::-1], kw1),
+        "split: kw0[0] for every block": (kw0, kw1, [kw0[0]] * 5, kw1),
+        "split: kw1 = kw0[0]": (kw0, kw1, kw0, kw0[0]),
+        "fold: kw0[0] for every block": ([kw0[0]] * 5, kw1, kw0, kw1),
+        "fold: kw1 = kw0[0]": (kw0, kw0[0], kw0, kw1),
+    }
+    for name, args in wrong.items():
+        err = _emulated_error(fx, p, sd, sd_np, *args)
+        print("%-32s max |emulated - f64| = %.3g" % (name, err))
+        assert not err <= 1e-2, (name, err)
