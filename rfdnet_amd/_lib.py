@@ -91,9 +91,7 @@ _SIZE_FNS = {"rfd_mise_vstate_elems": [_i, _i], "rfd_mise_dirty_elems": [_i, _i]
 _lib = None
 
 # Lazily built, cached artefacts (packed weight streams, folded BatchNorms, stacked weights) are shared by every host
-# thread that runs the same network (bench.py: several scenes in flight on one model).  A miss is built under this lock,
-# and published -- the building stream drained -- before it is stored, so a thread that finds the entry may use it on
-# ITS stream at once.
+# thread that runs the same network (bench.py: several scenes in flight on one model): build_once() builds them.
 import threading as _threading
 BUILD_LOCK = _threading.RLock()
 
@@ -103,6 +101,25 @@ def publish(device=None):
     import torch
     if torch.cuda.is_available():
         torch.cuda.current_stream(device).synchronize()
+
+
+def build_once(store, slot, key, build, device, limit=None):
+    """store[slot] = (key, build()) unless it already holds `key`; -> the value.  The one way a shared artefact is
+    built: a miss is built under BUILD_LOCK, published on `device` (if a CUDA device) and stored in one assignment, so
+    a thread that finds it may use it on its own stream at once.  A per-object cache passes its __dict__ and a fixed
+    slot name, a multi-entry one its dict with slot = key, and `limit`: it is cleared when it holds more entries."""
+    hit = store.get(slot)
+    if hit is None or hit[0] != key:
+        with BUILD_LOCK:
+            hit = store.get(slot)
+            if hit is None or hit[0] != key:
+                value = build()
+                if limit is not None and len(store) > limit:
+                    store.clear()
+                if getattr(device, "type", None) == "cuda":
+                    publish(device)
+                hit = store[slot] = (key, value)
+    return hit[1]
 
 
 class RfdHipError(RuntimeError):

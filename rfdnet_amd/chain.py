@@ -23,22 +23,6 @@ def usable(x, P, d_in):
     return ok and d_in == 64 and x.stride(0) % 4 == 0 and x.data_ptr() % 16 == 0
 
 
-def _cached(key, build):
-    """shared by every host thread running the same network: a miss is built under the library's build lock and published
-    (building stream drained) before it is stored (_lib.BUILD_LOCK)"""
-    hit = _cache.get(key)
-    if hit is None:
-        with _lib.BUILD_LOCK:
-            hit = _cache.get(key)
-            if hit is None:
-                hit = build()
-                if len(_cache) > 64:
-                    _cache.clear()
-                _lib.publish(hit[0].device)
-                _cache[key] = hit
-    return hit
-
-
 def _packed(mode, layers):
     (W1, _), (W2, _), (W3, _) = layers
     key = tuple((None if w is None else (w.data_ptr(), w._version, tuple(w.shape))) for w in (W1, W2, W3)) + (mode,)
@@ -58,7 +42,7 @@ def _packed(mode, layers):
         _lib.check(rc, "rfd_chain_pack")
         torch.cuda.current_stream(W2.device).synchronize()          # w?c may be temporaries
         return (buf, sw1, sw2, sw3, (W1, W2, W3))                    # keep the keyed tensors alive
-    return _cached(key, build)
+    return _lib.build_once(_cache, key, key, build, W2.device, limit=64)
 
 
 def chain_pool(x, layer1, layer2, layer3, P, relu3):
@@ -107,7 +91,7 @@ def _head_packed(Wa, Wb, Wc):
         _lib.check(rc, "rfd_head_pack")
         torch.cuda.current_stream(Wa.device).synchronize()
         return (buf, swa, swb, swc, (Wa, Wb, Wc))
-    return _cached(key, build)
+    return _lib.build_once(_cache, key, key, build, Wa.device, limit=64)
 
 
 def head_scores(x, P, Wa, gbias, layer_b, layer_c, Wd, bd):

@@ -8,7 +8,7 @@ bias + ReLU fused in its epilogue.
 import torch
 import torch.nn.functional as F
 
-from . import gemm
+from . import _lib, gemm
 
 
 def folded(layer, bn=None):
@@ -19,19 +19,10 @@ def folded(layer, bn=None):
            None if bn is None else (bn.running_mean._version, bn.running_var._version,
                                     None if bn.weight is None else bn.weight._version,
                                     None if bn.bias is None else bn.bias._version))
-    hit = layer.__dict__.get('_folded')
-    if hit is not None and hit[0] == key:
-        return hit[1], hit[2]
-    from . import _lib
-    with _lib.BUILD_LOCK:                    # shared across host threads: built once, published before it is stored
-        hit = layer.__dict__.get('_folded')
-        if hit is not None and hit[0] == key:
-            return hit[1], hit[2]
-        return _fold_now(layer, bn, w, key)
+    return _lib.build_once(layer.__dict__, '_folded', key, lambda: _fold_now(layer, bn, w), w.device)
 
 
-def _fold_now(layer, bn, w, key):
-    from . import _lib
+def _fold_now(layer, bn, w):
     W = w.detach().reshape(w.shape[0], -1)
     b = layer.bias.detach() if layer.bias is not None else torch.zeros(W.shape[0], device=W.device, dtype=W.dtype)
     if bn is not None:
@@ -41,11 +32,7 @@ def _fold_now(layer, bn, w, key):
         beta = bn.bias.detach() if bn.bias is not None else torch.zeros_like(s)
         W = W * s[:, None]
         b = (b - bn.running_mean) * s + beta
-    W, b = W.contiguous(), b.contiguous()
-    if W.is_cuda:
-        _lib.publish(W.device)
-    layer.__dict__['_folded'] = (key, W, b)
-    return W, b
+    return W.contiguous(), b.contiguous()
 
 
 def linear_rows_pooled(x, W, b, rows_per_group, relu=True):

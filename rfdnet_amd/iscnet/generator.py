@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from .. import _lib
-from .occ_decoder import TILE
+from .occ_decoder import TILE, run_with_range_fallback
 
 
 class Mesh(object):
@@ -252,20 +252,8 @@ class Generator3D(object):
         dev = c.device if c is not None and c.is_cuda else torch.device(device)
         v = torch.as_tensor(np.ascontiguousarray(vertices, dtype=np.float64)).to(dev)
         with torch.no_grad():
-            table, fc_p_w = dec.fold(z.reshape(1, -1).float().to(dev), c.reshape(1, -1).float().to(dev))
-            ka_used = dec.ka
-            nrm = dec.normals(v, [0, v.shape[0]], table, fc_p_w)
-            with torch.cuda.device(dev):
-                st = _lib.stream_status_bits()
-            if st & 2:
-                with _lib.BUILD_LOCK:
-                    lowered = dec.lower_activation_scale()
-                if lowered or dec.ka < ka_used:
-                    table, fc_p_w = dec.fold(z.reshape(1, -1).float().to(dev), c.reshape(1, -1).float().to(dev))
-                    nrm = dec.normals(v, [0, v.shape[0]], table, fc_p_w)
-                    with torch.cuda.device(dev):
-                        st = (st & ~2) | _lib.stream_status_bits()
-            _lib.raise_status(st)
+            z, c = z.reshape(1, -1).float().to(dev), c.reshape(1, -1).float().to(dev)
+            nrm = run_with_range_fallback(dec, lambda: dec.normals(v, [0, v.shape[0]], *dec.fold(z, c)), dev)
         return nrm.cpu().numpy()
 
     def extract_mesh(self, occ_hat, z=None, c=None):

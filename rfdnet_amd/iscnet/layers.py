@@ -124,23 +124,19 @@ class ResnetPointnet(nn.Module):
         blk = getattr(self, 'block_%d' % i)
         key = (blk.fc_0.weight._version, blk.fc_1.weight._version, blk.shortcut.weight._version,
                blk.fc_0.weight.data_ptr())
-        c = self.__dict__.setdefault('_stack_cache', {})
-        if c.get(i, (None,))[0] != key:
-            from .. import _lib
-            with _lib.BUILD_LOCK:      # shared across host threads: built once, published before it is stored
-                if c.get(i, (None,))[0] != key:
-                    w0, ws = blk.fc_0.weight.detach(), blk.shortcut.weight.detach()
-                    wide = i == 0                                   # block 0: all 2h input columns are per-point
-                    first = (w0 if wide else w0[:, :h]).contiguous()
-                    second = torch.cat([blk.fc_1.weight.detach(), ws if wide else ws[:, :h]], 1).contiguous()
-                    entry = (key, first, second, None if wide else w0[:, h:].contiguous(),
-                             None if wide else ws[:, h:].contiguous(),
-                             # both pooled-half matrices and both biases stacked: ONE small GEMM per block
-                             None if wide else torch.cat([w0[:, h:], ws[:, h:]], 0).contiguous(),
-                             None if wide else torch.cat([blk.fc_0.bias.detach(), blk.fc_1.bias.detach()]).contiguous())
-                    _lib.publish(second.device)
-                    c[i] = entry
-        return (blk,) + c[i][1:]
+
+        def build():
+            w0, ws = blk.fc_0.weight.detach(), blk.shortcut.weight.detach()
+            wide = i == 0                                   # block 0: all 2h input columns are per-point
+            return ((w0 if wide else w0[:, :h]).contiguous(),
+                    torch.cat([blk.fc_1.weight.detach(), ws if wide else ws[:, :h]], 1).contiguous(),
+                    None if wide else w0[:, h:].contiguous(), None if wide else ws[:, h:].contiguous(),
+                    # both pooled-half matrices and both biases stacked: ONE small GEMM per block
+                    None if wide else torch.cat([w0[:, h:], ws[:, h:]], 0).contiguous(),
+                    None if wide else torch.cat([blk.fc_0.bias.detach(), blk.fc_1.bias.detach()]).contiguous())
+        from .. import _lib
+        return (blk,) + _lib.build_once(self.__dict__.setdefault('_stack_cache', {}), i, key, build,
+                                        blk.fc_0.weight.device)
 
     def frag_usable(self, B, T):
         """can forward_frag run this shape (B proposals x T points)?"""

@@ -215,25 +215,15 @@ class ISCNet(nn.Module):
         before: a StatusSnapshot taken in front of the completion -- flags in it belong to the stages before (raised as
         _StageFlag for reconstruct() to answer) and are looked at FIRST: the decoder's scale is not touched on their
         account."""
-        from .. import _lib
+        from .occ_decoder import run_with_range_fallback
         gen = self.completion.generator
-        dec = self.completion.decoder
         run = gen.generate_grids if return_grids else gen.generate_mesh
-        ka_used = dec.ka                     # the decoder is shared by the scenes in flight: see reconstruct()
-        out = run(codes, cls)
-        with torch.cuda.device(device):
-            st = _lib.stream_status_bits()
-        if before is not None and before.read():
-            raise _StageFlag(before.read())
-        if st & 2:
-            with _lib.BUILD_LOCK:
-                lowered = dec.lower_activation_scale()
-            if lowered or dec.ka < ka_used:  # this run was folded at a scale that has come down since: once more
-                out = run(codes, cls)
-                with torch.cuda.device(device):
-                    st = (st & ~2) | _lib.stream_status_bits()
-        _lib.raise_status(st)
-        return out
+
+        def stage_flags():
+            if before.read():
+                raise _StageFlag(before.read())
+        return run_with_range_fallback(self.completion.decoder, lambda: run(codes, cls), device,
+                                       None if before is None else stage_flags)
 
     @staticmethod
     def check_device_status(device):

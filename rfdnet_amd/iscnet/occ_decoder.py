@@ -22,6 +22,30 @@ MODE_F16X1 = 1   # throughput mode
 TILE = 128
 
 
+def run_with_range_fallback(dec, run, device, before=None):
+    """out = run() (the fold and the launches) with the stream's status read that must follow it.  An activation beyond
+    the f16 range (status bit 2) does not fail the call: run() is called once more when the decoder's scale has come
+    down since the first run began -- by this call (dec.lower_activation_scale()), or by another host thread sharing
+    the decoder (its run was folded at the OLD scale).  Only a flag raised at the fallback scale is a real overflow.
+    before(): called after the status read and before the scale is looked at -- it raises for the flags of earlier
+    stages, which must not lower the decoder's scale."""
+    ka_used = dec.ka
+    out = run()
+    with torch.cuda.device(device):
+        st = _lib.stream_status_bits()
+    if before is not None:
+        before()
+    if st & 2:
+        with _lib.BUILD_LOCK:
+            lowered = dec.lower_activation_scale()
+        if lowered or dec.ka < ka_used:
+            out = run()
+            with torch.cuda.device(device):
+                st = (st & ~2) | _lib.stream_status_bits()
+    _lib.raise_status(st)
+    return out
+
+
 class CBatchNorm1d(nn.Module):
     """Parameter container of layers.py:193-242 (conv_gamma, conv_beta, bn)."""
 
@@ -91,7 +115,6 @@ class DecoderCBatchNorm(nn.Module):
         # the reference's fp32 decoder (occ_decoder.py:110-123) cannot overflow, so neither may this one fail a scene
         self.ka = occ_fold.KA
         self.check_range = True        # forward() reads the stream's status word after the launch
-        self._packed = None            # (packed stream, kw0, kw1, key)
 
     # ---- weight stream (re-packed only when the parameters change) -----------
     def _weights_key(self):
@@ -100,60 +123,36 @@ class DecoderCBatchNorm(nn.Module):
         return tuple((p.data_ptr(), p._version, str(p.device)) for p in ps)
 
     def packed_weights(self):
-        key = self._weights_key() + (self.kernel,)
-        hit = self._packed
-        if hit is not None and hit[3] == key:
-            return hit[:3]
-        with _lib.BUILD_LOCK:          # shared across host threads: built once, published before it is stored
-            hit = self._packed
-            if hit is not None and hit[3] == key:
-                return hit[:3]
-            sd = {k: v.detach() for k, v in self.state_dict().items()}
-            fc0, fc1 = occ_fold.stacked_fc_weights(sd)
-            if not fc0.is_cuda:
-                raise RuntimeError("CPU not supported")
-            kw0 = [occ_fold.choose_kw([fc0[i]]) for i in range(5)]
-            kw1 = occ_fold.choose_kw([fc1])
-            packed = torch.empty(_lib.lib().rfd_occ_packed_bytes(), dtype=torch.uint8,
-                                 device=fc0.device)
-            arr = (C.c_int * 5)(*kw0)
-            with torch.cuda.device(fc0.device):
-                pack = _lib.lib().rfd_occ_pack_weights_w8 if self.kernel == "w8" else _lib.lib().rfd_occ_pack_weights
-                rc = pack(fc0.data_ptr(), fc1.data_ptr(), arr, kw1, packed.data_ptr(), _lib.current_stream())
-            _lib.check(rc, "rfd_occ_pack_weights")
-            _lib.publish(fc0.device)
-            self._packed = (packed, kw0, kw1, key)      # one tuple, one store: readers never see a half-updated pair
-        return self._packed[:3]
+        """The decoder kernels' weight stream: -> (packed, kw0, kw1)."""
+        return self._packed_stream('_packed', bwd=False)
 
     def packed_weights_bwd(self):
         """The weight stream of the normals kernel's backward pass (csrc/occ_normals.hip): rfd_occ_pack_weights_w8 of
         fc0' = blocks[4-j].fc_1.weight^T and fc1' = blocks[4-j].fc_0.weight^T.  Cached under packed_weights()'s key.
         Returns (packed, kb0, kb1)."""
+        return self._packed_stream('_packed_bwd', bwd=True)
+
+    def _packed_stream(self, slot, bwd):
         key = self._weights_key() + (self.kernel,)
-        hit = getattr(self, "_packed_bwd", None)
-        if hit is not None and hit[3] == key:
-            return hit[:3]
-        with _lib.BUILD_LOCK:
-            hit = getattr(self, "_packed_bwd", None)
-            if hit is not None and hit[3] == key:
-                return hit[:3]
+
+        def build():
             sd = {k: v.detach() for k, v in self.state_dict().items()}
             fc0, fc1 = occ_fold.stacked_fc_weights(sd)
             if not fc0.is_cuda:
                 raise RuntimeError("CPU not supported")
-            b0 = fc1.flip(0).transpose(1, 2).contiguous()          # W1^T of blocks 4 .. 0
-            b1 = fc0.flip(0).transpose(1, 2).contiguous()          # W0^T of blocks 4 .. 0
-            kb0 = [occ_fold.choose_kw([b0[j]]) for j in range(5)]
-            kb1 = occ_fold.choose_kw([b1])
+            if bwd:
+                fc0, fc1 = (fc1.flip(0).transpose(1, 2).contiguous(),      # W1^T of blocks 4 .. 0
+                            fc0.flip(0).transpose(1, 2).contiguous())      # W0^T of blocks 4 .. 0
+            k0 = [occ_fold.choose_kw([fc0[i]]) for i in range(5)]
+            k1 = occ_fold.choose_kw([fc1])
             packed = torch.empty(_lib.lib().rfd_occ_packed_bytes(), dtype=torch.uint8, device=fc0.device)
-            arr = (C.c_int * 5)(*kb0)
+            name = "rfd_occ_pack_weights_w8" if bwd or self.kernel == "w8" else "rfd_occ_pack_weights"
             with torch.cuda.device(fc0.device):
-                rc = _lib.lib().rfd_occ_pack_weights_w8(b0.data_ptr(), b1.data_ptr(), arr, kb1, packed.data_ptr(),
-                                                        _lib.current_stream())
-            _lib.check(rc, "rfd_occ_pack_weights_w8")
-            _lib.publish(fc0.device)
-            self._packed_bwd = (packed, kb0, kb1, key)
-        return self._packed_bwd[:3]
+                rc = getattr(_lib.lib(), name)(fc0.data_ptr(), fc1.data_ptr(), (C.c_int * 5)(*k0), k1,
+                                               packed.data_ptr(), _lib.current_stream())
+            _lib.check(rc, name)
+            return packed, k0, k1
+        return _lib.build_once(self.__dict__, slot, key, build, self.blocks[0].fc_0.weight.device)
 
     def normals(self, verts, vend, table, fc_p_w, return_grad=False):
         """Vertex normals -g / |g|, g = d logit / d p, of K meshes in one launch (csrc/occ_normals.hip;
@@ -200,21 +199,11 @@ class DecoderCBatchNorm(nn.Module):
             c = c.squeeze(2)
         verts = p.detach().reshape(-1, 3).double().contiguous()
         vend = [b * T for b in range(B + 1)]
-        ka_used = self.ka
-        table, fc_p_w = self.fold(z.detach().float(), c.detach().float())
-        _, grad = self.normals(verts, vend, table, fc_p_w, return_grad=True)
-        if self.check_range:
-            with torch.cuda.device(p.device):
-                st = _lib.stream_status_bits()
-            if st & 2:
-                with _lib.BUILD_LOCK:
-                    lowered = self.lower_activation_scale()
-                if lowered or self.ka < ka_used:
-                    table, fc_p_w = self.fold(z.detach().float(), c.detach().float())
-                    _, grad = self.normals(verts, vend, table, fc_p_w, return_grad=True)
-                    with torch.cuda.device(p.device):
-                        st = (st & ~2) | _lib.stream_status_bits()
-            _lib.raise_status(st)
+
+        def run():
+            table, fc_p_w = self.fold(z.detach().float(), c.detach().float())
+            return self.normals(verts, vend, table, fc_p_w, return_grad=True)[1]
+        grad = run_with_range_fallback(self, run, p.device) if self.check_range else run()
         return grad.view(B, T, 3)
 
     def _fc_out_bias(self):
@@ -233,18 +222,14 @@ class DecoderCBatchNorm(nn.Module):
                 sd["fc_z.weight"] = torch.zeros(256, 0, device=c.device)
                 sd["fc_z.bias"] = torch.zeros(256, device=c.device)
             return occ_fold.fold_table(sd, z, c, kw0, kw1, ka=self.ka)
+        ka = self.ka
         key = tuple((p.data_ptr(), p._version) for p in self.parameters()) + \
-            tuple((b.data_ptr(), b._version) for b in self.buffers()) + (self.ka,)
-        hit = getattr(self, "_fold_cache", None)
-        if hit is None or hit[0] != key:
-            with _lib.BUILD_LOCK:
-                hit = getattr(self, "_fold_cache", None)
-                if hit is None or hit[0] != key:
-                    sd = {k: v.detach() for k, v in self.state_dict().items()}
-                    consts = occ_fold.stacked_constants(sd, kw0, kw1, ka=self.ka)
-                    _lib.publish(c.device)
-                    hit = self._fold_cache = (key, consts)
-        return occ_fold.fold_table_stacked(hit[1], z, c)
+            tuple((b.data_ptr(), b._version) for b in self.buffers()) + (ka,)
+
+        def build():
+            sd = {k: v.detach() for k, v in self.state_dict().items()}
+            return occ_fold.stacked_constants(sd, kw0, kw1, ka=ka)
+        return occ_fold.fold_table_stacked(_lib.build_once(self.__dict__, '_fold_cache', key, build, c.device), z, c)
 
     def lower_activation_scale(self):
         """After status bit 2 (an activation * 2^ka reached the f16 limit): switch to the fallback scale, once.
@@ -315,8 +300,6 @@ class DecoderCBatchNorm(nn.Module):
         B, T, _ = p.shape
         if c.dim() == 3:
             c = c.squeeze(2)
-        ka_used = self.ka                  # (a decoder shared by several host threads may be lowered by another one)
-        table, fc_p_w = self.fold(z.float(), c.float())
         tpad = (T + TILE - 1) // TILE * TILE
         if tpad != T:
             pp = torch.zeros(B, tpad, 3, dtype=torch.float32, device=p.device)
@@ -325,21 +308,13 @@ class DecoderCBatchNorm(nn.Module):
             pp = p.contiguous().float()
         tiles_per = tpad // TILE
         tile_prop = torch.arange(B, dtype=torch.int32, device=p.device).repeat_interleave(tiles_per)
-        logits = self.decode_tiles(pp.reshape(-1, 3), tile_prop, table, fc_p_w)
-        if self.check_range:
-            # the module's own forward is synchronous about the f16-range flag (one 4-byte read on this stream):
-            # an overflow at the default scale is answered by the fallback scale, not by an exception
-            with torch.cuda.device(p.device):
-                st = _lib.stream_status_bits()
-            if st & 2:
-                with _lib.BUILD_LOCK:
-                    lowered = self.lower_activation_scale()
-            if st & 2 and (lowered or self.ka < ka_used):
-                table, fc_p_w = self.fold(z.float(), c.float())
-                logits = self.decode_tiles(pp.reshape(-1, 3), tile_prop, table, fc_p_w)
-                with torch.cuda.device(p.device):
-                    st = (st & ~2) | _lib.stream_status_bits()
-            _lib.raise_status(st)
+
+        def run():
+            table, fc_p_w = self.fold(z.float(), c.float())
+            return self.decode_tiles(pp.reshape(-1, 3), tile_prop, table, fc_p_w)
+        # the module's own forward is synchronous about the f16-range flag (one 4-byte read on this stream): an
+        # overflow at the default scale is answered by the fallback scale, not by an exception
+        logits = run_with_range_fallback(self, run, p.device) if self.check_range else run()
         return logits.view(B, tpad)[:, :T]
 
 

@@ -180,15 +180,10 @@ class PointSeg(nn.Module):
             g = linear_rows_pooled(h, *folded(enc.conv3, enc.bn3), P, relu=False)   # (B,1024), product never written
         # head conv1 on cat([global (1024, per proposal), pointfeat (64, per point)]) + bn1
         W, b = folded(self.conv1, self.bn1)
-        c = self.__dict__.get('_head_split')
-        if c is None or c[0] is not W:                       # per-point / per-proposal column halves
-            from .. import _lib
-            with _lib.BUILD_LOCK:      # shared across host threads: built once, published before it is stored
-                c = self.__dict__.get('_head_split')
-                if c is None or c[0] is not W:
-                    c = (W, W[:, 1024:].contiguous(), W[:, :1024].contiguous(), torch.zeros_like(b))
-                    _lib.publish(W.device)
-                    self.__dict__['_head_split'] = c
+        from .. import _lib
+        # per-point / per-proposal column halves, rebuilt when folded() returns another W (kept: its id is the key)
+        c = _lib.build_once(self.__dict__, '_head_split', id(W), lambda: (
+            W, W[:, 1024:].contiguous(), W[:, :1024].contiguous(), torch.zeros_like(b)), W.device)
         gbias = F.linear(g, c[2], b).contiguous()                              # (B,512): conv1's global-feature share + bias
         if chain.head_usable(pointfeat, P, self.k):
             # conv1 (point-feature columns) -> conv2 -> conv3 -> conv4 in one kernel (csrc/pointseg_chain.hip)
