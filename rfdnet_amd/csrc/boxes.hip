@@ -7,8 +7,10 @@
 //     triangulation of its 8 corners + find_simplex over all N scan points
 //     (net_utils/libs.py:128-137), keeping boxes with >= 5 points.  A box's
 //     convex hull is the box itself, so this is a point-in-oriented-box test:
-//     |(p-c).u| <= l/2, |(p-c).v| <= w/2, |p_z-c_z| <= h/2 with u = (cos a,
-//     sin a, 0), v = (-sin a, cos a, 0) in the scan's (depth) frame.
+//     |(p-c).u| <= |l|/2, |(p-c).v| <= |w|/2, |p_z-c_z| <= |h|/2 with u = (cos a,
+//     sin a, 0), v = (-sin a, cos a, 0) in the scan's (depth) frame.  The
+//     decoded size (mean + residual) is not bounded below; a negative extent
+//     only permutes the corners, the hull is that of the positive one.
 //   * nms_3d_faster_samecls (net_utils/nms.py:79-118): boxes sorted by
 //     objectness probability; the best survivor is picked, every other
 //     survivor OF THE SAME CLASS whose axis-aligned IoU with it exceeds
@@ -26,7 +28,7 @@ __global__ __launch_bounds__(256) void points_in_boxes_kernel(
     int *__restrict__ counts) {
   const int k = blockIdx.x, bi = blockIdx.y, K = gridDim.x;
   const double *b = boxes + ((size_t)bi * K + k) * 7;
-  const double cx = b[0], cy = b[1], cz = b[2], hl = 0.5 * b[3], hw = 0.5 * b[4], hh = 0.5 * b[5];
+  const double cx = b[0], cy = b[1], cz = b[2], hl = fabs(0.5 * b[3]), hw = fabs(0.5 * b[4]), hh = fabs(0.5 * b[5]);
   const double ca = cos(b[6]), sa = sin(b[6]);
   const float *p = pts + (size_t)bi * n * stride;
   int c = 0;

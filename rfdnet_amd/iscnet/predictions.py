@@ -74,7 +74,11 @@ def box_corners_upright_camera(center, size, angle):
 
 @torch.no_grad()
 def parse_predictions(end_points, point_clouds, dataset_config, config=None):
-    """-> (eval_dict {'pred_mask' (B,K) uint8 tensor}, parsed dict).  Device tensors."""
+    """-> (eval_dict {'pred_mask' (B,K) uint8 tensor}, parsed dict).  Device tensors.
+
+    A scene in which no box holds 5 scan points (remove_empty_box) has nothing to pick from: the reference stops on
+    `assert len(pick) > 0` (ap_helper.py:256); here its row of pred_mask is all zero, get_proposal_id returns an empty
+    (1, 0, 1) selection and ISCNet.generate(selection='nms') no meshes."""
     cfg = dict(DEFAULT_EVAL_CONFIG)
     cfg.update(config or {})
     if getattr(dataset_config, 'placeholder_sizes', False):
