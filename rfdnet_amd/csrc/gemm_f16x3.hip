@@ -23,17 +23,12 @@
 // Operands are pre-scaled by 2^sa / 2^sw (exact) to keep the lo parts in the
 // normal f16 range; the epilogue multiplies by 2^-(sa+sw).
 #include "common.h"
+#include "split_f16.h"
 #include <stdlib.h>
 
 namespace {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half2v __attribute__((ext_vector_type(2)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void lds_void;
-typedef const __attribute__((address_space(1))) void gbl_void;
+using namespace split_f16;
 
 constexpr int BM = 128, BN = 128, BK = 32;
 constexpr int A_STAGE_BYTES = (BM / 32) * (BK / 16) * 2 * 1024;  // 4 rowblocks x 2 ksteps x (hi,lo) x 1 KiB = 16 KiB
@@ -57,26 +52,14 @@ __global__ void gemm_pack_w_kernel(int N, int K, int sw, const float *__restrict
   const int n = ntile * BN + nb * 32 + (lane & 31);
   const int k = kiter * BK + ks * 16 + 8 * (lane >> 5) + j;
   const float w = ldexpf(W[(size_t)n * K + k], sw);
-  const _Float16 hi = (_Float16)w;
-  const _Float16 lo = (_Float16)(w - (float)hi);
-  packed[e] = split == 0 ? hi : lo;
+  packed[e] = weight_half(w, split);
 }
 
 // running maximum of |hi| words (two f16 per register): an activation that reaches the f16 limit
 // (|a| 2^sa >= 65504: cvt_pkrtz saturates, the product is silently wrong where the reference's
 // fp32 GEMM is not) raises bit 2 of the device status word, as the decoder does (occ_decoder.hip)
 __device__ __forceinline__ unsigned amax_u16(unsigned acc, unsigned hiw, bool nonneg) {
-  unsigned r;
-  const unsigned a = nonneg ? hiw : (hiw & 0x7fff7fffu);
-  asm("v_pk_max_u16 %0, %1, %2" : "=v"(r) : "v"(acc), "v"(a));
-  return r;
-}
-__device__ __forceinline__ void flag_overflow(unsigned amax16, unsigned *status) {
-  if ((amax16 & 0xffffu) >= 0x7bffu || (amax16 >> 16) >= 0x7bffu) atomicOr(status, 4u);
-}
-
-__device__ __forceinline__ f32x16 mfma(half8 a, half8 b, f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
+  return pk_max_u16(acc, nonneg ? hiw : (hiw & 0x7fff7fffu));
 }
 
 struct Args {
@@ -204,9 +187,9 @@ __global__ __launch_bounds__(256, 2) void gemm_f16x3_kernel(Args g) {
       for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-          acc[i][j] = mfma(ah[i], bh[j], acc[i][j]);
-          acc[i][j] = mfma(ah[i], bl[j], acc[i][j]);
-          acc[i][j] = mfma(al[i], bh[j], acc[i][j]);
+          acc[i][j] = mfma32(ah[i], bh[j], acc[i][j]);
+          acc[i][j] = mfma32(ah[i], bl[j], acc[i][j]);
+          acc[i][j] = mfma32(al[i], bh[j], acc[i][j]);
         }
     }
     if (more) store_a(st ^ 1, ar);
@@ -214,7 +197,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f16x3_kernel(Args g) {
     __syncthreads();
   }
 
-  flag_overflow(amax16, g.status);
+  flag_f16_range(amax16, g.status, 4u);
   // ---- epilogue: scale back, add bias / group bias / residual, ReLU, store
   const int half = lane >> 5, nl = lane & 31;
   float omax = 0.f;
@@ -276,9 +259,7 @@ __global__ void gemm_pack_rows_kernel(int N, int K, int sw, const float *__restr
   const int n = ntile * RN + blk * 32 + (lane & 31);
   const int k = piece * RK + 16 * (lane >> 5) + 8 * kstep + j;
   const float w = ldexpf(W[(size_t)n * K + k], sw);
-  const _Float16 hi = (_Float16)w;
-  const _Float16 lo = (_Float16)(w - (float)hi);
-  packed[e] = split == 0 ? hi : lo;
+  packed[e] = weight_half(w, split);
 }
 
 template <int N>
@@ -567,12 +548,12 @@ __global__ __launch_bounds__(512) void gemm_rows8_kernel(Args g) {
             }
           }
           const int b0 = 2 * bp, b1 = 2 * bp + 1;
-          acc[b0] = mfma(c[0][0], h0, acc[b0]);
-          acc[b1] = mfma(c[1][0], h0, acc[b1]);
-          acc[b0] = mfma(c[0][0], l0, acc[b0]);
-          acc[b1] = mfma(c[1][0], l0, acc[b1]);
-          acc[b0] = mfma(c[0][1], h0, acc[b0]);
-          acc[b1] = mfma(c[1][1], h0, acc[b1]);
+          acc[b0] = mfma32(c[0][0], h0, acc[b0]);
+          acc[b1] = mfma32(c[1][0], h0, acc[b1]);
+          acc[b0] = mfma32(c[0][0], l0, acc[b0]);
+          acc[b1] = mfma32(c[1][0], l0, acc[b1]);
+          acc[b0] = mfma32(c[0][1], h0, acc[b0]);
+          acc[b1] = mfma32(c[1][1], h0, acc[b1]);
           conv_slice(s == 0 ? xs : (xs ^ 1), s ^ 1, bp);
           if (s == 1 && load_next && bp < 2) load_x2(xs, bp);
           if (!(bp & 1)) dma(doff, (ps + 3) & 3, 2 * s + (bp >> 1));
@@ -653,13 +634,13 @@ __global__ void gemm_pack_frag_kernel(int N, int K, int sw, const float *__restr
   const int n = ntile * RN + blk * 32 + (lane & 31);
   const int k = piece * RK + frag_channel(kstep, lane >> 5, j);
   const float w = ldexpf(W[(size_t)n * K + k], sw);
-  const _Float16 hi = (_Float16)w;
-  const _Float16 lo = (_Float16)(w - (float)hi);
-  packed[e] = split == 0 ? hi : lo;
+  packed[e] = weight_half(w, split);
 }
 
-// (hi, lo) words of two scaled, rectified values
-__device__ __forceinline__ void split2(float a0, float a1, unsigned &hw, unsigned &lw) {
+// (hi, lo) words of two scaled values, the remainder by plain subtraction (v_cvt_f32_f16 + v_sub_f32) where
+// split_f16.h's split2 issues one mixed-precision fma: same values, another instruction stream -- this file keeps the
+// one its kernels were measured and audited with (so do store_a and conv_slice above, and pos_embed.hip's frag kernel)
+__device__ __forceinline__ void split2_sub(float a0, float a1, unsigned &hw, unsigned &lw) {
   const half2v h2 = __builtin_bit_cast(half2v, __builtin_amdgcn_cvt_pkrtz(a0, a1));
   const float r0 = a0 - (float)h2[0], r1 = a1 - (float)h2[1];
   hw = __builtin_bit_cast(unsigned, h2);
@@ -688,14 +669,14 @@ __global__ __launch_bounds__(256) void rows_to_frag_kernel(int M, int C, const f
       for (int e = 0; e < 4; e += 2) {
         float a0 = v[e] * a_scale, a1 = v[e + 1] * a_scale;
         if (relu) { a0 = a0 > 0.f ? a0 : 0.f; a1 = a1 > 0.f ? a1 : 0.f; }
-        split2(a0, a1, hw[2 * q + e / 2], lw[2 * q + e / 2]);
+        split2_sub(a0, a1, hw[2 * q + e / 2], lw[2 * q + e / 2]);
         amax16 = amax_u16(amax16, hw[2 * q + e / 2], false);
       }
     }
     *reinterpret_cast<u32x4 *>(dst + s * 2048) = u32x4{hw[0], hw[1], hw[2], hw[3]};
     *reinterpret_cast<u32x4 *>(dst + s * 2048 + 1024) = u32x4{lw[0], lw[1], lw[2], lw[3]};
   }
-  flag_overflow(amax16, status);
+  flag_f16_range(amax16, status, 4u);
 }
 
 // frag rows -> fp32 rows: (hi + lo) 2^-sa (exact: 22 significant bits)
@@ -736,7 +717,7 @@ __device__ __forceinline__ void frag_epilogue(const Args &g, const f32x16 (&acc)
 #pragma unroll
     for (int w = 0; w < 8; ++w) {
       const float a0 = acc[b][2 * w], a1 = acc[b][2 * w + 1];
-      split2((a0 > 0.f ? a0 : 0.f) * post, (a1 > 0.f ? a1 : 0.f) * post, hw[w], lw[w]);
+      split2_sub((a0 > 0.f ? a0 : 0.f) * post, (a1 > 0.f ? a1 : 0.f) * post, hw[w], lw[w]);
       amax16 = amax_u16(amax16, hw[w], true);
     }
     unsigned char *d = dst + b * FRAG_BLOCK_BYTES;
@@ -746,7 +727,7 @@ __device__ __forceinline__ void frag_epilogue(const Args &g, const f32x16 (&acc)
     *reinterpret_cast<u32x4 *>(d + 3072) = u32x4{lw[4], lw[5], lw[6], lw[7]};
   }
   // cvt_pkrtz saturates at 65504 = 0x7bff: a stored hi word that large means the value left the f16 range
-  flag_overflow(amax16, g.status);
+  flag_f16_range(amax16, g.status, 4u);
 }
 
 // Row-owner GEMM on frag rows, PERSISTENT: one workgroup per CU walks its list of 256 x 256 tiles (same n tile, so the
@@ -937,12 +918,12 @@ __global__ __launch_bounds__(512) void gemm_rowsf_kernel(Args g) {
               }
             }
             const int b0 = 2 * bp, b1 = 2 * bp + 1;
-            acc[b0] = mfma(c[0][0], h0, acc[b0]);
-            acc[b1] = mfma(c[1][0], h0, acc[b1]);
-            acc[b0] = mfma(c[0][0], l0, acc[b0]);
-            acc[b1] = mfma(c[1][0], l0, acc[b1]);
-            acc[b0] = mfma(c[0][1], h0, acc[b0]);
-            acc[b1] = mfma(c[1][1], h0, acc[b1]);
+            acc[b0] = mfma32(c[0][0], h0, acc[b0]);
+            acc[b1] = mfma32(c[1][0], h0, acc[b1]);
+            acc[b0] = mfma32(c[0][0], l0, acc[b0]);
+            acc[b1] = mfma32(c[1][0], l0, acc[b1]);
+            acc[b0] = mfma32(c[0][1], h0, acc[b0]);
+            acc[b1] = mfma32(c[1][1], h0, acc[b1]);
             if (!(bp & 1)) dma(doff, (ps + 3) & 3, 2 * s + (bp >> 1));
 #pragma unroll
             for (int q = 0; q < 6; ++q) {

@@ -31,14 +31,12 @@
 // Roofline: 1 312 768 FLOP per query point vs 16 B of HBM traffic => MFMA
 // bound.  F16X3 issues 3x the algorithmic MFMA work (peak = 2.5 PF/3).
 #include "common.h"
+#include "split_f16.h"
 #include "../../include/rfd_occ.h"
 
 namespace {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half2v __attribute__((ext_vector_type(2)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using namespace split_f16;
 
 constexpr int H = RFD_OCC_HIDDEN;
 constexpr int NB = RFD_OCC_BLOCKS;
@@ -87,14 +85,7 @@ __global__ void pack_weights_kernel(const float *__restrict__ fc0_w,
     kw = kw1;
   }
   const float w = ldexpf(W[(size_t)out_ch * H + in_ch], kw);
-  const _Float16 hi = (_Float16)w;  // round-to-nearest
-  const _Float16 lo = (_Float16)(w - (float)hi);
-  packed[e] = s == 0 ? hi : lo;
-}
-
-// ---- helpers --------------------------------------------------------------------
-__device__ __forceinline__ f32x16 mfma(half8 a, half8 b, f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
+  packed[e] = weight_half(w, s);
 }
 
 // ---- activation epilogue, in slices -------------------------------------------
@@ -116,36 +107,14 @@ __device__ __forceinline__ EpiTab load_epi_tab(const float *s_row, const float *
   return e;
 }
 
-// running max of packed non-negative f16 pairs, compared as u16 (monotone)
-__device__ __forceinline__ unsigned pk_max_u16(unsigned a, unsigned b) {
-  unsigned r;
-  asm("v_pk_max_u16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-  return r;
-}
-
 template <bool WITH_LO>
 __device__ __forceinline__ void epi_slice(int i, const f32x16 &x, const EpiTab &tb, unsigned (&hiw)[8],
                                           unsigned (&low)[8], unsigned &amax16) {
   const int q = i >> 1, e0 = 2 * (i & 1);
-  float a0 = __builtin_fmaf(tb.s[q][e0], x[2 * i], tb.t[q][e0]);
-  float a1 = __builtin_fmaf(tb.s[q][e0 + 1], x[2 * i + 1], tb.t[q][e0 + 1]);
-  a0 = a0 > 0.f ? a0 : 0.f;
-  a1 = a1 > 0.f ? a1 : 0.f;
-  const half2v h2 = __builtin_bit_cast(half2v, __builtin_amdgcn_cvt_pkrtz(a0, a1));  // round to zero
-  hiw[i] = __builtin_bit_cast(unsigned, h2);
-  amax16 = pk_max_u16(amax16, hiw[i]);
-  if (WITH_LO) {
-    // a - (float)hi (exact): one v_fma_mix_f32 per value, reading the f16 halves in place
-    float r0, r1;
-    asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(r0) : "v"(hiw[i]), "v"(a0));
-    asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r1) : "v"(hiw[i]), "v"(a1));
-    low[i] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(r0, r1));
-  } else {
-    low[i] = 0u;
-  }
+  act2<WITH_LO>(x[2 * i], x[2 * i + 1], tb.s[q][e0], tb.s[q][e0 + 1], tb.t[q][e0], tb.t[q][e0 + 1], hiw[i], low[i],
+                amax16);
 }
 
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ half8 words_to_frag(const unsigned (&w)[8], int o) {
   u32x4 v = {w[o], w[o + 1], w[o + 2], w[o + 3]};
   return __builtin_bit_cast(half8, v);
@@ -160,9 +129,6 @@ constexpr int HALF_FRAGS = 32;                                // fragments per h
 constexpr int HALF_BYTES = HALF_FRAGS * FRAG_HALVES * 2;      // 32 KiB
 constexpr int N_HALVES = NB * 8 * 2;                          // 80
 constexpr int SMEM_BYTES = SMEM_TAB_BYTES + 4 * HALF_BYTES;
-
-typedef __attribute__((address_space(3))) void lds_void;
-typedef const __attribute__((address_space(1))) void gbl_void;
 
 // One 1-KiB LDS-DMA piece (global_load_lds_dwordx4: lane-linear destination =
 // the fragment layout).  Half-chunk h = fragments [32h, 32h+32) of the stream:
@@ -276,10 +242,10 @@ __global__ __launch_bounds__(256) void occ_decode_kernel(
             fh = w[(2 * ks + 2) * 64];
             if (X3) fl = w[(2 * ks + 3) * 64];
           }
-          acc_cur = mfma(ch, ahi[ks], acc_cur);
+          acc_cur = mfma32(ch, ahi[ks], acc_cur);
           if (X3) {
-            acc_cur = mfma(ch, alo[ks], acc_cur);
-            acc_cur = mfma(cl, ahi[ks], acc_cur);
+            acc_cur = mfma32(ch, alo[ks], acc_cur);
+            acc_cur = mfma32(cl, ahi[ks], acc_cur);
           }
           if (kb < 7) {
 #pragma unroll
@@ -329,10 +295,10 @@ __global__ __launch_bounds__(256) void occ_decode_kernel(
             for (int q = 0; q < 8; ++q)
               if (X3 || !(q & 1)) g[q] = w2[q * 64];
           }
-          acc_next = mfma(ch, ahi[ks], acc_next);
+          acc_next = mfma32(ch, ahi[ks], acc_next);
           if (X3) {
-            acc_next = mfma(ch, alo[ks], acc_next);
-            acc_next = mfma(cl, ahi[ks], acc_next);
+            acc_next = mfma32(ch, alo[ks], acc_next);
+            acc_next = mfma32(cl, ahi[ks], acc_next);
           }
           if (ks < 8) epi_slice<X3>(ks, acc_cur, tb, hw, lw, amax16);  // VALU under the MFMAs
           {  // ONE LDS-DMA piece per step: four waves x 1 KiB per 96-cycle step keeps the
@@ -390,21 +356,21 @@ __global__ __launch_bounds__(256) void occ_decode_kernel(
             if (X3 || !(q & 1)) g[q] = w2[(8 * (p + 1) + q) * 64];
         }
         const int o0 = 2 * p, o1 = 2 * p + 1;
-        Hs[o0] = mfma(cf[0], bhi0, Hs[o0]);
-        Hs[o1] = mfma(cf[4], bhi0, Hs[o1]);
+        Hs[o0] = mfma32(cf[0], bhi0, Hs[o0]);
+        Hs[o1] = mfma32(cf[4], bhi0, Hs[o1]);
         if (X3) {
-          Hs[o0] = mfma(cf[0], blo0, Hs[o0]);
-          Hs[o1] = mfma(cf[4], blo0, Hs[o1]);
-          Hs[o0] = mfma(cf[1], bhi0, Hs[o0]);
-          Hs[o1] = mfma(cf[5], bhi0, Hs[o1]);
+          Hs[o0] = mfma32(cf[0], blo0, Hs[o0]);
+          Hs[o1] = mfma32(cf[4], blo0, Hs[o1]);
+          Hs[o0] = mfma32(cf[1], bhi0, Hs[o0]);
+          Hs[o1] = mfma32(cf[5], bhi0, Hs[o1]);
         }
-        Hs[o0] = mfma(cf[2], bhi1, Hs[o0]);
-        Hs[o1] = mfma(cf[6], bhi1, Hs[o1]);
+        Hs[o0] = mfma32(cf[2], bhi1, Hs[o0]);
+        Hs[o1] = mfma32(cf[6], bhi1, Hs[o1]);
         if (X3) {
-          Hs[o0] = mfma(cf[2], blo1, Hs[o0]);
-          Hs[o1] = mfma(cf[6], blo1, Hs[o1]);
-          Hs[o0] = mfma(cf[3], bhi1, Hs[o0]);
-          Hs[o1] = mfma(cf[7], bhi1, Hs[o1]);
+          Hs[o0] = mfma32(cf[2], blo1, Hs[o0]);
+          Hs[o1] = mfma32(cf[6], blo1, Hs[o1]);
+          Hs[o0] = mfma32(cf[3], bhi1, Hs[o0]);
+          Hs[o1] = mfma32(cf[7], bhi1, Hs[o1]);
         }
         if (p < 3) {
 #pragma unroll
@@ -444,8 +410,7 @@ __global__ __launch_bounds__(256) void occ_decode_kernel(
   part += __shfl_xor(part, 32);
   if (half == 0) logits[pidx] = part + fc_out_b;
   }  // persistent tile loop
-  // 0x7bff = 65504 = largest finite f16: the round-to-zero conversion saturates there
-  if ((amax16 & 0xffffu) >= 0x7bffu || (amax16 >> 16) >= 0x7bffu) atomicOr(status, 2u);
+  flag_f16_range(amax16, status, 2u);
 }
 
 }  // namespace

@@ -16,6 +16,7 @@
 // pack kernel orders every weight matrix's columns accordingly, so activations never leave
 // the lane (as in the 4-wave kernel).
 #include "common.h"
+#include "split_f16.h"
 #include <stdlib.h>
 #include <type_traits>
 #include "../../include/rfd_occ.h"
@@ -27,12 +28,7 @@
 // source built without any switch is this kernel, instruction for instruction.
 namespace {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half2v __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void lds_void;
-typedef const __attribute__((address_space(1))) void gbl_void;
+using namespace split_f16;
 
 constexpr int H = RFD_OCC_HIDDEN;
 constexpr int NB = RFD_OCC_BLOCKS;
@@ -121,37 +117,7 @@ __global__ void pack8_kernel(const float *__restrict__ fc0_w, const float *__res
     kw = kw1;
   }
   const float w = ldexpf(W[(size_t)out_ch * H + in_ch], kw);
-  const _Float16 hi = (_Float16)w;
-  _Float16 lo = (_Float16)(w - (float)hi);
-  packed[e] = s == 0 ? hi : lo;
-}
-
-__device__ __forceinline__ f32x4 mfma16(half8 a, half8 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ unsigned pk_max_u16(unsigned a, unsigned b) {
-  unsigned r;
-  asm("v_pk_max_u16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-  return r;
-}
-
-// relu(s x + t) of two values -> packed f16 hi (round to zero) and lo words
-template <bool WITH_LO>
-__device__ __forceinline__ void act2(float x0, float x1, float s0, float s1, float t0, float t1, unsigned &hiw,
-                                     unsigned &low, unsigned &amax16) {
-  float a0 = __builtin_fmaf(s0, x0, t0), a1 = __builtin_fmaf(s1, x1, t1);
-  a0 = a0 > 0.f ? a0 : 0.f;
-  a1 = a1 > 0.f ? a1 : 0.f;
-  hiw = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(a0, a1));
-  amax16 = pk_max_u16(amax16, hiw);
-  if (WITH_LO) {
-    float r0, r1;
-    asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(r0) : "v"(hiw), "v"(a0));
-    asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r1) : "v"(hiw), "v"(a1));
-    low = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(r0, r1));
-  } else {
-    low = 0u;
-  }
+  packed[e] = weight_half(w, s);
 }
 
 // the two channel tiles of one k-step -> B fragment pair; S / T rows at channel 32 ks
@@ -209,10 +175,6 @@ __device__ __forceinline__ void dma_piece8(const half8 *__restrict__ packed, uns
 // The loads themselves are plain loads: hipcc counts them (lgkmcnt) and pads the MFMA-SrcC write-after-read states
 // itself.  (An asm-issued variant measured 1 % faster in one build and returned WRONG logits in another: hipcc may
 // copy an asm load's destination register before the data has landed -- it does not know the load is in flight.)
-struct Frag4 {
-  half8 h0, l0, h1, l1;
-};
-
 __device__ __forceinline__ void keep_alive(const Frag4 &a, const Frag4 &b) {
   asm volatile("" ::"v"(a.h0), "v"(a.l0), "v"(a.h1), "v"(a.l1), "v"(b.h0), "v"(b.l0), "v"(b.h1), "v"(b.l1));
 }
@@ -231,14 +193,6 @@ __device__ __forceinline__ void frag_issue(Frag4 &d, const half8 *base) {
 
 // Nothing is scheduled across a k-step boundary (see above).
 __device__ __forceinline__ void step_fence() { __builtin_amdgcn_sched_barrier(0); }
-
-template <int I, int N, class F>
-__device__ __forceinline__ void static_for(F &&f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>{});
-    static_for<I + 1, N>(f);
-  }
-}
 
 template <int TERMS>
 __global__ __launch_bounds__(512) void occ_decode8_kernel(
@@ -505,7 +459,7 @@ __global__ __launch_bounds__(512) void occ_decode8_kernel(
     if (!claim) break;
     next_chunk(t_begin, t_end);
   }
-  if ((amax16 & 0xffffu) >= 0x7bffu || (amax16 >> 16) >= 0x7bffu) atomicOr(status, 2u);
+  flag_f16_range(amax16, status, 2u);
   if (claim) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the last tile's unused ring prefetch has landed
     if (tid() == 0) {

@@ -13,8 +13,8 @@
 //
 // Arithmetic: every accumulator sees the SAME sequence of matrix instructions as in occ_decode8_kernel (per k-step: W_hi a_hi,
 // W_hi a_lo, W_lo a_hi; k-steps in order), the same fc_p / CBN / fc_out code around them -- the logits are bit-identical
-// (tests/test_gpu_decoder.py asserts it).  The helpers below are copies of occ_decoder8.hip's: that file is frozen
-// (tests/test_isa_audit.py pins its instruction stream) and stays untouched.
+// (tests/test_gpu_decoder.py asserts it).  The conversion, the range watch and the fragment / S-T fetch helpers are
+// split_f16.h's, shared with occ_decoder8.hip and occ_normals.hip.
 //
 // Two waves of this kernel share a SIMD and nothing orders them, so one wave's prologue (fc_p) runs beside the other's matrix
 // instructions: the first build of this file returned wrong 16-point groups until the library was compiled with
@@ -22,6 +22,7 @@
 // beside another wave's v_mfma on gfx950 (profiles/r06_pk_f32_hazard.txt, tools/hazard/; tests/test_isa_audit.py keeps the
 // form out of every kernel).
 #include "common.h"
+#include "split_f16.h"
 #include "../../include/rfd_occ.h"
 
 int rfd_occ_tail_launch(int n_tiles, const float *pts, const int *tile_prop, const int *tile_src, const void *packed,
@@ -31,9 +32,7 @@ int rfd_occ_tail_launch(int n_tiles, const float *pts, const int *tile_prop, con
 
 namespace {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+using namespace split_f16;
 
 constexpr int H = RFD_OCC_HIDDEN;
 constexpr int NB = RFD_OCC_BLOCKS;
@@ -42,45 +41,6 @@ constexpr int ROWS = RFD_OCC_TABLE_ROWS;
 constexpr int HALF_FRAGS = 32;                 // fragments (1 KiB each) per half of the packed stream
 constexpr int DEPTH = 3;                       // k-steps of weight fragments in flight ahead of the one in use
 constexpr int SETS = DEPTH + 1;
-
-__device__ __forceinline__ f32x4 mfma16(half8 a, half8 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ unsigned pk_max_u16(unsigned a, unsigned b) {
-  unsigned r;
-  asm("v_pk_max_u16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-  return r;
-}
-
-// relu(s x + t) of two values -> packed f16 hi (round to zero) and lo words (occ_decoder8.hip act2)
-template <bool WITH_LO>
-__device__ __forceinline__ void act2(float x0, float x1, float s0, float s1, float t0, float t1, unsigned &hiw,
-                                     unsigned &low, unsigned &amax16) {
-  float a0 = __builtin_fmaf(s0, x0, t0), a1 = __builtin_fmaf(s1, x1, t1);
-  a0 = a0 > 0.f ? a0 : 0.f;
-  a1 = a1 > 0.f ? a1 : 0.f;
-  hiw = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(a0, a1));
-  amax16 = pk_max_u16(amax16, hiw);
-  if (WITH_LO) {
-    float r0, r1;
-    asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(r0) : "v"(hiw), "v"(a0));
-    asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r1) : "v"(hiw), "v"(a1));
-    low = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(r0, r1));
-  } else {
-    low = 0u;
-  }
-}
-
-// the S / T values of one k-step's two channel tiles
-struct ST {
-  f32x4 s0, t0, s1, t1;
-};
-__device__ __forceinline__ void st_issue(ST &d, const float *S, const float *T, int ch) {
-  d.s0 = *reinterpret_cast<const f32x4 *>(S + ch);
-  d.t0 = *reinterpret_cast<const f32x4 *>(T + ch);
-  d.s1 = *reinterpret_cast<const f32x4 *>(S + ch + 16);
-  d.t1 = *reinterpret_cast<const f32x4 *>(T + ch + 16);
-}
 
 template <bool WITH_LO>
 __device__ __forceinline__ void act_kstep(const f32x4 &x0, const f32x4 &x1, const ST &c, half8 &hi, half8 &lo,
@@ -92,26 +52,6 @@ __device__ __forceinline__ void act_kstep(const f32x4 &x0, const f32x4 &x1, cons
   act2<WITH_LO>(x1[2], x1[3], c.s1[2], c.s1[3], c.t1[2], c.t1[3], hw[3], lw[3], amax16);
   hi = __builtin_bit_cast(half8, u32x4{hw[0], hw[1], hw[2], hw[3]});
   lo = __builtin_bit_cast(half8, u32x4{lw[0], lw[1], lw[2], lw[3]});
-}
-
-struct Frag4 {
-  half8 h0, l0, h1, l1;
-};
-// k-step ks of half h: fragments 4 ks .. 4 ks + 3 = (hi, lo) of two channel tiles, 4 KiB in one piece
-__device__ __forceinline__ void frag_issue(Frag4 &d, const half8 *half_base, int ks) {
-  const half8 *w = half_base + ks * 256;
-  d.h0 = w[0];
-  d.l0 = w[64];
-  d.h1 = w[128];
-  d.l1 = w[192];
-}
-
-template <int I, int N, class F>
-__device__ __forceinline__ void static_for(F &&f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>{});
-    static_for<I + 1, N>(f);
-  }
 }
 
 template <int TERMS>
@@ -262,7 +202,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
       logits[pidx] = part + fc_out_b;
     }
   }
-  if ((amax16 & 0xffffu) >= 0x7bffu || (amax16 >> 16) >= 0x7bffu) atomicOr(status, 2u);
+  flag_f16_range(amax16, status, 2u);
 }
 
 }  // namespace

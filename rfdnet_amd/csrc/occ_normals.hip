@@ -3,8 +3,8 @@
 //
 // Shape: the tail decoder's (occ_decoder_tail.hip) -- ONE wave per workgroup, 16 vertices, no LDS, no barrier, weight
 // fragments straight from L2 one k-step ahead, 16x16x32 MFMAs on (hi, lo) f16 splits (three products per k-step, fp32
-// accumulation).  The helpers are copies of that file's (occ_decoder8.hip and occ_decoder_tail.hip stay untouched: their
-// instruction streams are pinned).
+// accumulation).  The conversion, the range watch and the fragment / S-T fetch helpers are split_f16.h's, shared with
+// that file.
 //
 // Forward pass: the decoder exactly as the tail kernel evaluates it (same table, same packed stream, same status bit 2 on an
 // activation beyond the f16 range), but nothing is kept of it except the ReLU masks of its 11 CBN layers.  In the D layout a
@@ -33,13 +33,13 @@
 // Groups of 16 vertices never span two meshes: gprefix[k] = first group of mesh k (K + 1 entries); a wave finds its mesh by
 // binary search, the last group of a mesh is masked.
 #include "common.h"
+#include "split_f16.h"
 #include "../../include/rfd_occ.h"
 
 namespace {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+using namespace split_f16;
+
 typedef unsigned long long u64;
 
 constexpr int H = RFD_OCC_HIDDEN;
@@ -55,25 +55,6 @@ struct Exps {
   int e1[NB], e0[NB];
 };
 
-__device__ __forceinline__ f32x4 mfma16(half8 a, half8 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ unsigned pk_max_u16(unsigned a, unsigned b) {
-  unsigned r;
-  asm("v_pk_max_u16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-  return r;
-}
-
-// x0, x1 -> packed f16 hi (round to zero) and lo words (occ_decoder8.hip act2 without the affine map); amax16 sees |hi|
-__device__ __forceinline__ void split2(float a0, float a1, unsigned &hiw, unsigned &low, unsigned &amax16) {
-  hiw = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(a0, a1));
-  amax16 = pk_max_u16(amax16, hiw & 0x7fff7fffu);
-  float r0, r1;
-  asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(r0) : "v"(hiw), "v"(a0));
-  asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r1) : "v"(hiw), "v"(a1));
-  low = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(r0, r1));
-}
-
 // relu(s x + t) of two values -> split, and their two ReLU mask bits (bit 0: x0, bit 1: x1)
 __device__ __forceinline__ unsigned act2m(float x0, float x1, float s0, float s1, float t0, float t1, unsigned &hiw,
                                           unsigned &low, unsigned &amax16) {
@@ -83,17 +64,6 @@ __device__ __forceinline__ unsigned act2m(float x0, float x1, float s0, float s1
   a1 = a1 > 0.f ? a1 : 0.f;
   split2(a0, a1, hiw, low, amax16);
   return m;
-}
-
-// the S / T values of one k-step's two channel tiles
-struct ST {
-  f32x4 s0, t0, s1, t1;
-};
-__device__ __forceinline__ void st_issue(ST &d, const float *S, const float *T, int ch) {
-  d.s0 = *reinterpret_cast<const f32x4 *>(S + ch);
-  d.t0 = *reinterpret_cast<const f32x4 *>(T + ch);
-  d.s1 = *reinterpret_cast<const f32x4 *>(S + ch + 16);
-  d.t1 = *reinterpret_cast<const f32x4 *>(T + ch + 16);
 }
 
 // forward: relu(S x + T) of one k-step's two tiles -> B fragment pair; returns the 8 mask bits (bit j = slot j)
@@ -124,27 +94,6 @@ __device__ __forceinline__ void grad_kstep(const f32x4 &x0, const f32x4 &x1, con
   for (int q = 0; q < 4; ++q) split2(v[2 * q], v[2 * q + 1], hw[q], lw[q], amax16);
   hi = __builtin_bit_cast(half8, u32x4{hw[0], hw[1], hw[2], hw[3]});
   lo = __builtin_bit_cast(half8, u32x4{lw[0], lw[1], lw[2], lw[3]});
-}
-
-struct Frag4 {
-  half8 h0, l0, h1, l1;
-};
-// k-step ks of half h: fragments 4 ks .. 4 ks + 3 = (hi, lo) of two channel tiles, 4 KiB in one piece
-// (half_base: wave-uniform, the lane's offset added last -- one scalar base per half, one lane offset for all of them)
-__device__ __forceinline__ void frag_issue(Frag4 &d, const half8 *half_base, int ks) {
-  const half8 *w = half_base + ks * 256 + threadIdx.x;
-  d.h0 = w[0];
-  d.l0 = w[64];
-  d.h1 = w[128];
-  d.l1 = w[192];
-}
-
-template <int I, int N, class F>
-__device__ __forceinline__ void static_for(F &&f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>{});
-    static_for<I + 1, N>(f);
-  }
 }
 
 // brings the point's max |g'| (its 4 lanes: n, n + 16, n + 32, n + 48) into [1, 2) by a power of two; returns the exponent
@@ -197,8 +146,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
   auto fetch = [&](auto kc, const half8 *cur, const half8 *next) {
     constexpr int ks = decltype(kc)::value;
     __builtin_amdgcn_sched_barrier(0);
-    if constexpr (ks + DEPTH < 8) frag_issue(fs[(ks + DEPTH) % SETS], cur, ks + DEPTH);
-    else frag_issue(fs[(ks + DEPTH) % SETS], next, ks + DEPTH - 8);
+    if constexpr (ks + DEPTH < 8) frag_issue(fs[(ks + DEPTH) % SETS], cur, ks + DEPTH, lane);
+    else frag_issue(fs[(ks + DEPTH) % SETS], next, ks + DEPTH - 8, lane);
   };
   auto mma = [&](f32x4 &a0, f32x4 &a1, const Frag4 &f, const half8 &xh, const half8 &xl) {
     a0 = mfma16(f.h0, xh, a0);
@@ -235,7 +184,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
   {
     const half8 *wl = packed_f;
     auto half_ptr = [&](int h) { return wl + (size_t)h * HALF_FRAGS * 64; };
-    static_for<0, DEPTH>([&](auto kc) { frag_issue(fs[decltype(kc)::value], half_ptr(0), decltype(kc)::value); });
+    static_for<0, DEPTH>([&](auto kc) { frag_issue(fs[decltype(kc)::value], half_ptr(0), decltype(kc)::value, lane); });
     for (int blk = 0; blk < NB; ++blk) {
       const float *S0 = tab + (1 + 4 * blk) * H, *T0 = S0 + H, *S1 = T0 + H, *T1 = S1 + H;
       u64 m0 = 0ull, m1 = 0ull;
@@ -415,7 +364,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
       grad[(size_t)v * 3 + 2] = ldexpf(d2, X);
     }
   }
-  if ((amax16 & 0xffffu) >= 0x7bffu || (amax16 >> 16) >= 0x7bffu) atomicOr(status, 2u);
+  flag_f16_range(amax16, status, 2u);
 }
 
 }  // namespace

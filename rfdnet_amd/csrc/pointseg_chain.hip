@@ -15,15 +15,12 @@
 // the two small layers' weights sit in LDS for the kernel's lifetime.  MODE: 1 = first layer d <= 8 on the VALU (STN3d),
 // 2 = first layer 64 -> 64 on the matrix cores (STNkd), 0 = no first layer (PointNetEncoder conv2 / conv3).
 #include "common.h"
+#include "split_f16.h"
 #include "../../include/rfd_occ.h"
 
 namespace {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void lds_void;
-typedef const __attribute__((address_space(1))) void gbl_void;
+using namespace split_f16;
 
 constexpr int C1 = 64, C2 = 128, C3 = 1024;           // C3: the LARGEST last-layer width (LDS is sized for it)
 constexpr int PIECE = 32 * 1024;                       // 4 output tiles of the last layer x (4 k-steps x hi, lo) x 1 KiB
@@ -37,10 +34,6 @@ constexpr int W1_BYTES = (C1 / 16) * 2 * 2 * 1024;     // 4 tiles x 2 k-steps x 
 constexpr int OFF_W2 = 3 * PIECE, OFF_W1 = OFF_W2 + W2_BYTES, OFF_B = OFF_W1 + W1_BYTES;
 constexpr int B_FLOATS = C1 + C2 + C3 + C1 * 8 + C3;   // b1, b2, b3, raw W1 (64 x 8), pooled maxima
 constexpr int SMEM = OFF_B + B_FLOATS * 4;             // 154 368 B
-
-__device__ __forceinline__ f32x4 mfma16(half8 a, half8 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-}
 
 // k order of a 32-wide k-step whose operand is a previous layer's accumulators: lane group kg, slot j
 __host__ __device__ inline int chain_k(int ks, int kg, int j) { return 32 * ks + 16 * (j >> 2) + 4 * kg + (j & 3); }
@@ -71,25 +64,7 @@ __global__ void chain_pack_kernel(int mode, int c3, const float *__restrict__ W1
     const int ks = (frag >> 1) & 1, tile = (int)(frag >> 2);
     w = mode == 2 ? ldexpf(W1[(size_t)(16 * tile + idx) * C1 + 32 * ks + 8 * kg + j], sw1) : 0.f;
   }
-  const _Float16 hi = (_Float16)w;
-  const _Float16 lo = (_Float16)(w - (float)hi);
-  packed[e] = split == 0 ? hi : lo;
-}
-
-__device__ __forceinline__ unsigned pk_max_u16(unsigned a, unsigned b) {
-  unsigned r;
-  asm("v_pk_max_u16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-  return r;
-}
-
-// two scaled values -> packed f16 hi (round to zero) and lo words
-__device__ __forceinline__ void split2(float a0, float a1, unsigned &hiw, unsigned &low, unsigned &amax16) {
-  hiw = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(a0, a1));
-  amax16 = pk_max_u16(amax16, hiw & 0x7fff7fffu);
-  float r0, r1;
-  asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(r0) : "v"(hiw), "v"(a0));
-  asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r1) : "v"(hiw), "v"(a1));
-  low = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(r0, r1));
+  packed[e] = weight_half(w, split);
 }
 
 // accumulators of channel tiles 2ks, 2ks+1 (+ bias, ReLU, scale) -> the next layer's operand fragment pair of k-step ks
@@ -323,7 +298,7 @@ __global__ __launch_bounds__(512) void chain_kernel(ChainArgs a) {
     // stored, like the row-owner GEMM's pool path does -- |o| 2^sa beyond f16 would saturate there silently
     if (fabsf(o) * a.ascale >= 65504.f) atomicOr(a.status, 4u);
   }
-  if ((amax16 & 0xffffu) >= 0x7bffu || (amax16 >> 16) >= 0x7bffu) atomicOr(a.status, 4u);
+  flag_f16_range(amax16, a.status, 4u);
 }
 
 // =====================================================================================================================
@@ -372,9 +347,7 @@ __global__ void head_pack_kernel(const float *__restrict__ Wa, const float *__re
     const int ks = (q >> 1) & 7, tt = q >> 4, tile = 2 * (piece - H_SLABS) + tt;
     w = ldexpf(Wc[(size_t)(16 * tile + idx) * HB + chain_k(ks, kg, j)], swc);
   }
-  const _Float16 hi = (_Float16)w;
-  const _Float16 lo = (_Float16)(w - (float)hi);
-  packed[e] = split == 0 ? hi : lo;
+  packed[e] = weight_half(w, split);
 }
 
 struct HeadArgs {
@@ -544,7 +517,7 @@ __global__ __launch_bounds__(512) void head_kernel(HeadArgs a) {
       if (a.n_cls > 1) a.out[row * a.n_cls + 1] = sc1 + s_bd[1];
     }
   }
-  if ((amax16 & 0xffffu) >= 0x7bffu || (amax16 >> 16) >= 0x7bffu) atomicOr(a.status, 4u);
+  flag_f16_range(amax16, a.status, 4u);
 }
 
 }  // namespace

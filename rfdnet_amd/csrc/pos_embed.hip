@@ -10,8 +10,11 @@
 // buffer the encoder's first GEMM reads; the torch composition (K = d GEMM + addcmul_) moved
 // three times as many bytes.
 #include "common.h"
+#include "split_f16.h"
 
 namespace {
+
+using namespace split_f16;
 
 constexpr int PE_THREADS = 256;
 constexpr int PE_MAX_D = 8;
@@ -63,9 +66,6 @@ __global__ __launch_bounds__(PE_THREADS) void pos_embed_kernel(
 // the consumer's matrix instruction.  A wave owns a 32-row block at a time and walks its N / 32 channel blocks; lane
 // (row, half) produces the 16 channels of its row the block assigns to it.  W[:, :d] and the bias sit in LDS (all
 // lanes of a half-wave read the same address: broadcast); HBM-bound on the 4 N bytes per row it writes.
-typedef unsigned pe_u4 __attribute__((ext_vector_type(4)));
-typedef _Float16 pe_h2 __attribute__((ext_vector_type(2)));
-
 template <int D>
 __global__ __launch_bounds__(PE_THREADS) void pos_embed_frag_kernel(
     int M, int N, int ldx, int rows_per_group, const float *__restrict__ x, const float *__restrict__ mask,
@@ -106,25 +106,22 @@ __global__ __launch_bounds__(PE_THREADS) void pos_embed_frag_kernel(
         }
 #pragma unroll
         for (int e = 0; e < 4; e += 2) {
-          const pe_h2 h2 = __builtin_bit_cast(pe_h2, __builtin_amdgcn_cvt_pkrtz(o[e], o[e + 1]));
+          const half2v h2 = __builtin_bit_cast(half2v, __builtin_amdgcn_cvt_pkrtz(o[e], o[e + 1]));
           const float r0 = o[e] - (float)h2[0], r1 = o[e + 1] - (float)h2[1];
           const unsigned h = __builtin_bit_cast(unsigned, h2);
           hw[2 * q + e / 2] = h;
           lw[2 * q + e / 2] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(r0, r1));
-          unsigned mx;
-          asm("v_pk_max_u16 %0, %1, %2" : "=v"(mx) : "v"(amax16), "v"(h));
-          amax16 = mx;
+          amax16 = pk_max_u16(amax16, h);
         }
       }
       unsigned char *d = dst + (size_t)kb * 4096;
-      *reinterpret_cast<pe_u4 *>(d) = pe_u4{hw[0], hw[1], hw[2], hw[3]};
-      *reinterpret_cast<pe_u4 *>(d + 1024) = pe_u4{lw[0], lw[1], lw[2], lw[3]};
-      *reinterpret_cast<pe_u4 *>(d + 2048) = pe_u4{hw[4], hw[5], hw[6], hw[7]};
-      *reinterpret_cast<pe_u4 *>(d + 3072) = pe_u4{lw[4], lw[5], lw[6], lw[7]};
+      *reinterpret_cast<u32x4 *>(d) = u32x4{hw[0], hw[1], hw[2], hw[3]};
+      *reinterpret_cast<u32x4 *>(d + 1024) = u32x4{lw[0], lw[1], lw[2], lw[3]};
+      *reinterpret_cast<u32x4 *>(d + 2048) = u32x4{hw[4], hw[5], hw[6], hw[7]};
+      *reinterpret_cast<u32x4 *>(d + 3072) = u32x4{lw[4], lw[5], lw[6], lw[7]};
     }
   }
-  // hi words are non-negative; cvt_pkrtz saturates at 65504 = 0x7bff
-  if ((amax16 & 0xffffu) >= 0x7bffu || (amax16 >> 16) >= 0x7bffu) atomicOr(status, 4u);
+  flag_f16_range(amax16, status, 4u);          // hi words are non-negative
 }
 
 }  // namespace

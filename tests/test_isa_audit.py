@@ -87,6 +87,10 @@ def test_shipped_kernels_carry_no_wrong_result_switch_and_the_ablation_patch_reb
                 line_start = text.rfind("\n", 0, m.start()) + 1
                 line = text[line_start:text.find("\n", m.start())]
                 assert "static const" in line or "(e = getenv" in line or "const char *to = getenv" in line, (name, line)
+        # the f16 (hi, lo) conversion, the packed running maximum and the range threshold have ONE definition
+        if name != "split_f16.h":
+            for token in ("v_pk_max_u16", "v_fma_mix_f32", "0x7bffu"):
+                assert token not in text, (name, token)
     shipped = _asm(tmp_path, "occ_decoder8.hip", "dec8_shipped.s")
     patched = _asm(tmp_path, _ablation_source(tmp_path), "dec8_patched.s")
     assert _code_lines(shipped) == _code_lines(patched)
