@@ -30,6 +30,11 @@ def build_parser():
     ap.add_argument("--resolution_0", type=int, default=None)
     ap.add_argument("--upsampling_steps", type=int, default=None)       # ISCNet_test.yaml:62-63 (32, 0)
     ap.add_argument("--selection", choices=["nms", "all", "objectness"], default="nms")
+    ap.add_argument("--gt", type=str, default=None,
+                    help="--mode test: .npz with the scan's ground-truth labels (center_label, heading_class_label, "
+                         "heading_residual_label, size_class_label, size_residual_label, sem_cls_label, "
+                         "box_label_mask); the scene then goes through ISCNet.evaluate and its box AP / recall at IoU "
+                         "0.25 and 0.5 are printed")
     ap.add_argument("--mean_size_npz", type=str, default=None,
                     help="class mean sizes (the reference's datasets/scannet/scannet_means.npz); default: "
                          "$RFD_MEAN_SIZE_NPZ or that path relative to the working directory")
@@ -82,9 +87,25 @@ def main():
     data = {k: v.cuda() for k, v in data.items()}
     torch.cuda.synchronize()
     t0 = time.time()
-    end_points, ids, meshes = net.generate(data, selection=args.selection)
+    records = None
+    if args.mode == "test" and args.gt:
+        gt = np.load(args.gt)
+        for k in ('center_label', 'heading_class_label', 'heading_residual_label', 'size_class_label',
+                  'size_residual_label', 'sem_cls_label', 'box_label_mask'):
+            a = np.asarray(gt[k])
+            per_scan = 2 if k in ('center_label', 'size_residual_label') else 1
+            data[k] = torch.from_numpy(a[None] if a.ndim == per_scan else a).cuda()      # one scan: add the batch axis
+        end_points, ids, meshes, records = net.evaluate(data)
+    else:
+        end_points, ids, meshes = net.generate(data, selection=args.selection)
     torch.cuda.synchronize()
     print('Time elapsed: %s.' % (time.time() - t0))                       # demo.py:411
+    if records is not None:
+        from rfdnet_amd.iscnet.evaluation import APCalculator
+        calc = APCalculator((0.25, 0.5))
+        calc.step(records)
+        for thr, metrics in zip((0.25, 0.5), calc.compute_metrics()):
+            print('IoU %g: %s' % (thr, {k: float(v) for k, v in metrics.items()}))
     box = keep = None
     if 'parsed_predictions' in end_points:
         box = end_points['parsed_predictions']['box_params'][0].cpu().numpy()

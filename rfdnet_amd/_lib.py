@@ -15,7 +15,7 @@ _f = C.c_void_p      # device pointers travel as integers (tensor.data_ptr())
 _i = C.c_int
 _fl = C.c_float
 
-# name -> argtypes, exactly the prototypes of include/rfd_pointnet2.h / rfd_occ.h / rfd_chamfer.h
+# name -> argtypes, exactly the prototypes of include/rfd_pointnet2.h / rfd_occ.h / rfd_chamfer.h / rfd_eval.h
 SIGNATURES = {
     "furthest_point_sampling_kernel_wrapper": [_i, _i, _i, _f, _f, _f, _f],
     "gather_points_kernel_wrapper": [_i, _i, _i, _i, _f, _f, _f, _f],
@@ -78,6 +78,8 @@ SIGNATURES = {
     "rfd_rows_to_frag": [_i, _i, _f, _i, _i, _i, _f, C.c_long, _f],
     "rfd_frag_to_rows": [_i, _i, _f, C.c_long, _i, _f, _i, _f],
     "rfd_gemm_f16x3_frag": [_i, _i, _i, _f, C.c_long, _f, _f, C.c_long, _f, _f, _i, _i, _i, _i, _f, _i, _f],
+    "rfd_box3d_iou": [_i, _i, _i, _f, _f, _f, _f, _f],
+    "rfd_ap_match": [_i, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _f, _f],
 }
 _RESTYPES = {
     "rfd_last_error_string": C.c_char_p,

@@ -1,0 +1,363 @@
+"""Detection evaluation: oriented-box IoU and true-positive matching on the device, mAP / AR on the host -- the
+counterpart of the tail of the reference's `--mode test` sweep:
+
+  parse_groundtruths   net_utils/ap_helper.py:326-368
+  scene_records        assembly_pred_map_cls + assembly_gt_map_cls without meshes (:267-323, :371-401) and the
+                       per-scene part of eval_det_cls_wo_mesh (net_utils/eval_det.py:304-331)
+  APCalculator         ap_helper.py:25-82 over eval_det.py:259-343, :424-473
+
+The reference moves every head output to the host, calls scipy's ConvexHull once per (detection, ground truth)
+pair and opens a multiprocessing Pool.  The ground truths' `det` flags are per scene and per class, so the matching is
+independent for each (scene, class, threshold) and runs where the boxes are: two kernels per scene
+(csrc/box_eval.hip) and one small device-to-host copy the host does not wait for; only the global sort by confidence and the cumulative sums are
+left to the host (compute_metrics).
+
+Deviations from the reference, both on inputs it cannot score: a pair on which scipy raises QhullError (no
+intersection area, a zero-volume box) has IoU 0; `evaluate_mesh=True` is not available (see APCalculator).
+Boxes with exactly coincident edges (exact copies, boxes touching along a face) are ill-posed for the reference's clip --
+its own IoU is arbitrary there, above 1 at times -- and the kernel's value, though finite, is no better (include/rfd_eval.h).
+A class with predictions and no ground truth has AP 0 and -- as in the reference, whose recall is 0 / 0 there -- a
+NaN recall, which makes 'AR' NaN.
+"""
+import numpy as np
+import torch
+
+from .. import _lib
+from . import predictions
+
+MAX_THRESHOLDS = 4
+LIST_GROUPS = 16384          # (scene, class) groups per launch pair of records_from_lists
+
+
+def _call(name, dev, *args):
+    with torch.cuda.device(dev):
+        rc = getattr(_lib.lib(), name)(*args, _lib.current_stream())
+    _lib.check(rc, name)
+
+
+def _thresholds(ap_iou_thresh):
+    thr = tuple(float(t) for t in np.atleast_1d(np.asarray(ap_iou_thresh, dtype=np.float64)))
+    if not 1 <= len(thr) <= MAX_THRESHOLDS:
+        raise ValueError("1 .. %d IoU thresholds, got %d" % (MAX_THRESHOLDS, len(thr)))
+    return thr
+
+
+@torch.no_grad()
+def parse_groundtruths(gt_data, dataset_config):
+    """Ground-truth labels -> {'sem_cls_label' (B,G), 'gt_corners_3d_upright_camera' (B,G,8,3) f64,
+    'box_label_mask' (B,G)}, device tensors; rows with box_label_mask == 0 are zero."""
+    center = gt_data['center_label'][:, :, 0:3].double()
+    nh = dataset_config.num_heading_bin
+    # class2angle / class2size (scannet_config.py:43-53, :71-73) in double, as the reference's numpy scalars
+    angle = gt_data['heading_class_label'].double() * (2 * np.pi / float(nh)) + gt_data['heading_residual_label'].double()
+    angle = torch.where(angle > np.pi, angle - 2 * np.pi, angle)
+    mean_size = torch.from_numpy(np.asarray(dataset_config.mean_size_arr, dtype=np.float64)).to(center.device)
+    size = mean_size[gt_data['size_class_label'].long()] + gt_data['size_residual_label'].double()
+    corners = predictions.box_corners_upright_camera(center, size, angle)
+    mask = gt_data['box_label_mask']
+    corners = corners * (mask != 0).view(*mask.shape, 1, 1).to(corners.dtype)
+    return {'sem_cls_label': gt_data['sem_cls_label'], 'gt_corners_3d_upright_camera': corners,
+            'box_label_mask': mask}
+
+
+def box3d_iou(pred_corners, gt_corners, with_2d=False):
+    """(B,K,8,3), (B,G,8,3) f64 device tensors -> iou3d (B,K,G) [, iou2d]: one rfd_box3d_iou launch."""
+    pred = pred_corners.double().contiguous()
+    gt = gt_corners.double().contiguous()
+    B, K = pred.shape[:2]
+    G = gt.shape[1]
+    iou3d = torch.zeros(B, K, G, dtype=torch.float64, device=pred.device)
+    iou2d = torch.zeros_like(iou3d) if with_2d else None
+    _call("rfd_box3d_iou", pred.device, B, K, G, pred.data_ptr(), gt.data_ptr(), iou3d.data_ptr(),
+          iou2d.data_ptr() if with_2d else None)
+    return (iou3d, iou2d) if with_2d else iou3d
+
+
+def ap_match(iou3d, order, det_valid, gt_cls, gt_valid, thr):
+    """One rfd_ap_match launch -> tp (nT,B,C,K) uint8; thr: (nT) f64 device tensor."""
+    B, C, K = order.shape
+    G = gt_cls.shape[1]
+    tp = torch.empty(thr.numel(), B, C, K, dtype=torch.uint8, device=order.device)
+    _call("rfd_ap_match", order.device, B, C, K, G, thr.numel(), iou3d.data_ptr(), order.data_ptr(),
+          det_valid.data_ptr(), gt_cls.data_ptr(), gt_valid.data_ptr(), thr.data_ptr(), tp.data_ptr())
+    return tp
+
+
+class SceneRecords(object):
+    """What one scene_records call leaves for the host: per (scene, class, detection) the score, whether it takes part
+    and its true-positive flag per threshold, plus the ground-truth count per (scene, class) -- packed into ONE pinned
+    buffer filled by one copy queued on the caller's stream.  The views score (B,C,K) f32, valid (B,C,K) u8,
+    tp (nT,B,C,K) u8 and npos (B,C) i32 are meaningful once `event` has passed; compact() waits for it (and for
+    nothing else) and returns the records as flat arrays
+    {'cls' (n) i32, 'score' (n) f32, 'tp' (nT,n) u8, 'npos' (C) i64, 'thr'}."""
+
+    def __init__(self, thr, shape, buf, event, timing=None):
+        B, C, K = shape
+        n = B * C * K
+        nT = len(thr)
+        self.thr, self.buf, self.event = thr, buf, event
+        self.score = buf[:4 * n].view(torch.float32).view(B, C, K)
+        self.npos = buf[4 * n:4 * n + 4 * B * C].view(torch.int32).view(B, C)
+        o = 4 * n + 4 * B * C
+        self.valid = buf[o:o + n].view(B, C, K)
+        self.tp = buf[o + n:o + n + nT * n].view(nT, B, C, K)
+        self.timing = timing                    # (start, end) events around the two launches, when asked for
+        self._compact = None
+
+    def device_ms(self):
+        self.event.synchronize()
+        return self.timing[0].elapsed_time(self.timing[1])
+
+    def compact(self):
+        if self._compact is None:
+            self.event.synchronize()
+            valid = self.valid.numpy() != 0
+            bi, ci, ki = np.nonzero(valid)
+            self._compact = {'cls': ci.astype(np.int32), 'score': self.score.numpy()[bi, ci, ki],
+                             'tp': self.tp.numpy()[:, bi, ci, ki], 'npos': self.npos.numpy().sum(0).astype(np.int64),
+                             'thr': self.thr}
+        return self._compact
+
+
+_thr_cache = {}
+
+
+def _device_thresholds(thr, dev):
+    """the thresholds as an f64 device tensor, uploaded once per (device, thresholds)"""
+    return _lib.build_once(_thr_cache, (str(dev), thr), (str(dev), thr),
+                           lambda: torch.tensor(thr, dtype=torch.float64, device=dev), dev, limit=64)
+
+
+def _records(pred_corners, score, valid, gt_corners, gt_cls, gt_valid, thr, timing=False):
+    """score (B,C,K) f32, valid (B,C,K) u8, gt_cls (B,G) i32, gt_valid (B,G) u8 on the device -> SceneRecords.
+    Everything is queued on the current stream and the host waits for none of it: an argsort and a few small tensor
+    kernels (ground-truth counts, packing), the two launches, and one device-to-host copy into pinned memory."""
+    dev = score.device
+    B, C, K = score.shape
+    stream = torch.cuda.current_stream(dev)
+    ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) if timing else None
+    # the global sort by confidence is the host's; within a (scene, class) only the order matters (stable, so equal
+    # scores go by index -- the reference's np.argsort(-confidence) leaves the order of ties undefined)
+    order = torch.argsort(score, dim=-1, descending=True, stable=True).int().contiguous()
+    thr_d = _device_thresholds(thr, dev)
+    if ev:
+        ev[0].record(stream)
+    iou3d = box3d_iou(pred_corners, gt_corners)
+    tp = ap_match(iou3d, order, valid, gt_cls, gt_valid, thr_d)
+    if ev:
+        ev[1].record(stream)
+    npos = ((gt_cls.unsqueeze(1) == torch.arange(C, device=dev, dtype=gt_cls.dtype).view(1, C, 1)) &
+            (gt_valid.unsqueeze(1) != 0)).sum(-1).int()
+    packed = torch.cat([score.contiguous().view(torch.uint8).flatten(), npos.contiguous().view(torch.uint8).flatten(),
+                        valid.flatten(), tp.flatten()])
+    buf = torch.empty(packed.shape, dtype=torch.uint8, pin_memory=True)
+    buf.copy_(packed, non_blocking=True)
+    done = torch.cuda.Event()
+    done.record(stream)
+    return SceneRecords(thr, (B, C, K), buf, done, ev)
+
+
+@torch.no_grad()
+def scene_records(eval_dict, parsed_predictions, parsed_gts, config=None, ap_iou_thresh=(0.25, 0.5), timing=False):
+    """Device tensors in (numpy is uploaded) -> SceneRecords, queued on the current stream; the host does not wait.
+    A detection takes part iff pred_mask == 1 and obj_prob > conf_thresh.  per_class_proposal (default): it is scored
+    for every class with sem_cls_probs[..., c] * obj_prob (a float32 product); otherwise once, for pred_sem_cls, with
+    obj_prob.  config: the eval config (predictions.DEFAULT_EVAL_CONFIG keys)."""
+    cfg = dict(predictions.DEFAULT_EVAL_CONFIG)
+    cfg.update(config or {})
+    thr = _thresholds(ap_iou_thresh)
+    corners = parsed_predictions['pred_corners_3d_upright_camera']
+    dev = corners.device if torch.is_tensor(corners) and corners.is_cuda else torch.device('cuda', torch.cuda.current_device())
+    as_t = lambda a, dt: (a if torch.is_tensor(a) else torch.as_tensor(np.asarray(a))).to(dev, dt)
+    corners = as_t(corners, torch.float64)
+    obj_prob = as_t(parsed_predictions['obj_prob'], torch.float32)
+    sem = as_t(parsed_predictions['sem_cls_probs'], torch.float32)
+    pred_cls = as_t(parsed_predictions['pred_sem_cls'], torch.int64)
+    mask = as_t(eval_dict['pred_mask'], torch.int64)
+    B, K, C = sem.shape
+    take = (mask == 1) & (obj_prob > cfg['conf_thresh'])
+    if cfg['per_class_proposal']:
+        score = (sem * obj_prob.unsqueeze(-1)).transpose(1, 2).contiguous()
+        valid = take.unsqueeze(1).expand(B, C, K)
+    else:
+        score = obj_prob.unsqueeze(1).expand(B, C, K).contiguous()
+        valid = take.unsqueeze(1) & (pred_cls.unsqueeze(1) == torch.arange(C, device=dev).view(1, C, 1))
+    gt_corners = as_t(parsed_gts['gt_corners_3d_upright_camera'], torch.float64)
+    gt_cls = as_t(parsed_gts['sem_cls_label'], torch.int32).contiguous()
+    gt_valid = (as_t(parsed_gts['box_label_mask'], torch.float32) == 1).to(torch.uint8).contiguous()
+    return _records(corners, score, valid.to(torch.uint8).contiguous(), gt_corners, gt_cls, gt_valid, thr, timing)
+
+
+def merge_records(records, thr=None, n_cls=0):
+    """A list of records (SceneRecords or compact dicts; one record alone is a list of one) -> one compact dict
+    {'cls' (n) i32, 'score' (n) f32, 'tp' (nT,n) u8, 'npos' (C) i64, 'thr'}.  An empty list needs `thr` and gives
+    n = 0 with n_cls zero counts."""
+    recs = [r.compact() if isinstance(r, SceneRecords) else r
+            for r in (records if isinstance(records, (list, tuple)) else [records])]
+    if thr is None:
+        if not recs:
+            raise ValueError("no records and no thresholds")
+        thr = recs[0]['thr']
+    thr = tuple(float(t) for t in thr)
+    if any(tuple(r['thr']) != thr for r in recs):
+        raise ValueError("records were matched at other IoU thresholds than %r" % (thr,))
+    npos = np.zeros(max([len(r['npos']) for r in recs] + [n_cls]), np.int64)
+    for r in recs:
+        npos[:len(r['npos'])] += np.asarray(r['npos'], np.int64)
+    cat = lambda parts, empty: np.concatenate(parts, -1) if parts else empty
+    return {'cls': cat([np.asarray(r['cls'], np.int32) for r in recs], np.zeros(0, np.int32)),
+            'score': cat([np.asarray(r['score'], np.float32) for r in recs], np.zeros(0, np.float32)),
+            'tp': cat([np.asarray(r['tp'], np.uint8).reshape(len(thr), -1) for r in recs], np.zeros((len(thr), 0), np.uint8)),
+            'npos': npos, 'thr': thr}
+
+
+VOC07_RECALL_GRID = np.arange(11) * 0.1
+
+
+def voc_ap(rec, prec, use_07_metric=True):
+    """Average precision of one class from its recall / precision after each detection (by descending score).
+    VOC 2007: the mean over the eleven recall levels 0, 0.1, ... 1 of the best precision reached at or beyond that
+    recall (0 if it is never reached).  The levels are k * 0.1 in floating point, as the reference's grid is: a recall
+    of exactly 3 / 10 does NOT reach the level 0.30000000000000004.
+    All points: the area under the precision envelope (at each detection the best precision from there on),
+    integrated over the recall steps."""
+    rec, prec = np.asarray(rec, np.float64), np.asarray(prec, np.float64)
+    if use_07_metric:
+        reached = rec[None, :] >= VOC07_RECALL_GRID[:, None]
+        return float(np.where(reached, prec[None, :], 0.).max(axis=1, initial=0.).sum() / 11.)
+    envelope = np.maximum.accumulate(prec[::-1])[::-1]
+    return float(np.sum(np.diff(rec, prepend=0.) * envelope))
+
+
+class APCalculator(object):
+    """ap_helper.py:25-82.  step() takes the records of scene_records (SceneRecords, or their compact() dict -- what
+    sharding.gather_records returns) or the reference's two lists; compute_metrics() returns the reference's dict
+    ('<cls> Average Precision', 'mAP', '<cls> Recall', 'AR'), or one such dict per threshold when `ap_iou_thresh` is a
+    sequence.
+
+    evaluate_mesh=True raises: the reference's mesh mAP voxelises every predicted and ground-truth mesh through the
+    external `binvox` program and loads the ShapeNet ground-truth meshes from disk; neither is available to this
+    project, so the result could not be checked against anything."""
+
+    def __init__(self, ap_iou_thresh=0.25, class2type_map=None, evaluate_mesh=False):
+        if evaluate_mesh:
+            raise NotImplementedError(
+                "evaluate_mesh=True: mesh mAP needs the external `binvox` voxeliser and the ShapeNet ground-truth "
+                "meshes (ap_helper.py:429-478); neither exists here, so it cannot be computed or pinned. "
+                "Box mAP (evaluate_mesh=False) is available.")
+        self.single = np.ndim(ap_iou_thresh) == 0
+        self.ap_iou_thresh = _thresholds(ap_iou_thresh)
+        self.class2type_map = class2type_map
+        self.evaluate_mesh = False
+        self.reset()
+
+    def reset(self):
+        self.records = []
+        self.scan_cnt = 0
+
+    def step(self, records, batch_gt_map_cls=None):
+        if batch_gt_map_cls is not None:
+            assert len(records) == len(batch_gt_map_cls)
+            self.scan_cnt += len(records)
+            records = records_from_lists(records, batch_gt_map_cls, self.ap_iou_thresh)
+        elif isinstance(records, SceneRecords):
+            self.scan_cnt += records.score.shape[0]
+        else:
+            self.scan_cnt += 1
+        if (records.thr if isinstance(records, SceneRecords) else tuple(records['thr'])) != self.ap_iou_thresh:
+            raise ValueError("records were matched at other IoU thresholds than %r" % (self.ap_iou_thresh,))
+        self.records.append(records)
+
+    def class_curves(self, ti, use_07_metric=True):
+        """-> {class: (rec, prec, ap)}; a class with ground truths and no prediction: (0, 0, 0) as in the reference"""
+        merged = merge_records(self.records, self.ap_iou_thresh)
+        cls, score, tp, npos = merged['cls'], merged['score'], merged['tp'][ti], merged['npos']
+        n_cls = len(npos)
+        out = {}
+        for c in range(n_cls):
+            m = cls == c
+            if not m.any():
+                if npos[c] > 0:
+                    out[c] = (0, 0, 0)
+                continue
+            o = np.argsort(-score[m], kind='stable')
+            flags = tp[m][o].astype(np.float64)
+            tpc, fpc = np.cumsum(flags), np.cumsum(1. - flags)
+            with np.errstate(divide='ignore', invalid='ignore'):
+                rec = tpc / float(npos[c])                     # 0 / 0 = NaN without ground truths, as the reference
+            prec = tpc / np.maximum(tpc + fpc, np.finfo(np.float64).eps)
+            out[c] = (rec, prec, voc_ap(rec, prec, use_07_metric))
+        return out
+
+    def compute_metrics(self, use_07_metric=True):
+        """use_07_metric=True is what the reference's compute_metrics_wo_mesh runs with (the default of
+        eval_det_multiprocessing_wo_mesh); False gives the all-points AP."""
+        rets = []
+        for ti in range(len(self.ap_iou_thresh)):
+            cur = self.class_curves(ti, use_07_metric)
+            name = lambda c: self.class2type_map[c] if self.class2type_map else str(c)
+            ret = {}
+            for c in sorted(cur):
+                ret['%s Average Precision' % name(c)] = cur[c][2]
+            ret['mAP'] = np.mean([cur[c][2] for c in sorted(cur)]) if cur else float('nan')
+            rec_list = []
+            for c in sorted(cur):
+                r = cur[c][0][-1] if np.ndim(cur[c][0]) else 0
+                ret['%s Recall' % name(c)] = r
+                rec_list.append(r)
+            ret['AR'] = np.mean(rec_list) if cur else float('nan')
+            rets.append(ret)
+        return rets[0] if self.single else rets
+
+
+def records_from_lists(batch_pred_map_cls, batch_gt_map_cls, ap_iou_thresh):
+    """The reference's list format (ap_helper.py:40-54: [[(cls, corners (8,3), score), ...], ...] and
+    [[(cls, corners), ...], ...]) through the same two kernels.  Detections and ground truths are grouped by (scene,
+    class) -- the unit the matching is independent in -- padded to the largest group and uploaded as one batch of
+    single-class scenes; more than 1024 detections or 256 ground truths in one group is the kernel's error."""
+    thr = _thresholds(ap_iou_thresh)
+    classes = sorted({int(p[0]) for lst in batch_pred_map_cls for p in lst} |
+                     {int(g[0]) for lst in batch_gt_map_cls for g in lst})
+    n_cls = (classes[-1] + 1) if classes else 0
+    assert not classes or classes[0] >= 0, "class ids are non-negative integers"
+    npos = np.zeros(n_cls, np.int64)
+    groups = {}                                    # (scene, class) -> ([boxes], [scores], [gt boxes])
+    for s, (preds, gts) in enumerate(zip(batch_pred_map_cls, batch_gt_map_cls)):
+        for g in gts:
+            npos[int(g[0])] += 1
+            groups.setdefault((s, int(g[0])), ([], [], []))[2].append(np.asarray(g[1], np.float64))
+        for p in preds:
+            e = groups.setdefault((s, int(p[0])), ([], [], []))
+            e[0].append(np.asarray(p[1], np.float64))
+            e[1].append(np.float32(p[2]))
+    keys = [k for k in sorted(groups) if groups[k][0]]
+    if not keys:
+        return {'cls': np.zeros(0, np.int32), 'score': np.zeros(0, np.float32),
+                'tp': np.zeros((len(thr), 0), np.uint8), 'npos': npos, 'thr': thr}
+    Kp = max(len(groups[k][0]) for k in keys)
+    Gp = max(max(len(groups[k][2]) for k in keys), 1)
+    b = len(keys)
+    corners = np.zeros((b, Kp, 8, 3))
+    score = np.full((b, 1, Kp), -np.inf, np.float32)
+    valid = np.zeros((b, 1, Kp), np.uint8)
+    gtc = np.zeros((b, Gp, 8, 3))
+    gt_valid = np.zeros((b, Gp), np.uint8)
+    for i, k in enumerate(keys):
+        boxes, sc, gts = groups[k]
+        corners[i, :len(boxes)] = np.stack(boxes)
+        score[i, 0, :len(sc)] = sc
+        valid[i, 0, :len(sc)] = 1
+        if gts:
+            gtc[i, :len(gts)] = np.stack(gts)
+            gt_valid[i, :len(gts)] = 1
+    dev = torch.device('cuda', torch.cuda.current_device())
+    up = lambda a: torch.from_numpy(a).to(dev)
+    # a whole sweep can hold more groups than one launch takes scenes (65535): a launch pair per LIST_GROUPS groups
+    parts = [_records(up(corners[i:i + LIST_GROUPS]), up(score[i:i + LIST_GROUPS]), up(valid[i:i + LIST_GROUPS]),
+                      up(gtc[i:i + LIST_GROUPS]), torch.zeros(min(LIST_GROUPS, b - i), Gp, dtype=torch.int32, device=dev),
+                      up(gt_valid[i:i + LIST_GROUPS]), thr) for i in range(0, b, LIST_GROUPS)]
+    rec = merge_records(parts, thr)
+    # compact() walks the (group, detection) pairs in row-major order: the class of a record is its group's
+    counts = valid[:, 0].sum(1, dtype=np.int64)
+    cls = np.repeat(np.array([k[1] for k in keys], np.int32), counts)
+    return {'cls': cls, 'score': rec['score'], 'tp': rec['tp'], 'npos': npos, 'thr': thr}

@@ -170,6 +170,27 @@ class ISCNet(nn.Module):
         out = self.reconstruct(end_points, proposal_features, ids, pc, return_grids=return_grids)
         return end_points, ids, out
 
+    def evaluate(self, data, fit=True, ap_iou_thresh=(0.25, 0.5), timing=False):
+        """The tail of the reference's `generate` in test mode (network.py:85-177): detection and completion with
+        selection='nms', then (fit) the box refinement of fit_mesh_to_scan, then the evaluation records of the --
+        refined -- boxes against the ground-truth labels in `data` (center_label, heading_class_label,
+        heading_residual_label, size_class_label, size_residual_label, sem_cls_label, box_label_mask).
+        -> (end_points, proposal ids, meshes, records): what generate returns plus evaluation.SceneRecords, queued on
+        the current stream (feed them to evaluation.APCalculator.step).  end_points['parsed_predictions'] holds the
+        corners that were scored."""
+        from . import evaluation
+        end_points, ids, meshes = self.generate(data, selection='nms')
+        parsed = end_points['parsed_predictions']
+        eval_dict = {'pred_mask': end_points['pred_mask']}
+        if fit and len(meshes):
+            parsed = self.fit_mesh_to_scan({'meshes': meshes, 'proposal_ids': ids}, parsed, eval_dict,
+                                           data['point_clouds'], self.cfg.config['generation']['dump_threshold'])
+            end_points['parsed_predictions'] = parsed
+        parsed_gts = evaluation.parse_groundtruths(data, self.cfg.dataset_config)
+        records = evaluation.scene_records(eval_dict, parsed, parsed_gts, getattr(self.cfg, 'eval_overrides', None),
+                                           ap_iou_thresh, timing=timing)
+        return end_points, ids, meshes, records
+
     def reconstruct(self, end_points, proposal_features, ids, pc, return_grids=False, hook=None):
         """skip propagation -> object codes -> occupancy completion for the selected proposals, with the status
         reads that must follow (see complete()).  A split-precision GEMM activation beyond the f16 range at the

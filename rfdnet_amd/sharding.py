@@ -343,3 +343,45 @@ def job_throughput(gathered):
     steps = gathered[:, STAT_FIELDS.index("steps")].sum()
     t_max = gathered[:, STAT_FIELDS.index("elapsed_s")].max()
     return float(steps / t_max), float(t_max)
+
+
+def gather_records(records, dist=None, device=None, thr=None):
+    """This rank's evaluation records (one or a list: iscnet.evaluation.SceneRecords or their compact() dicts) -> the
+    whole job's as one compact dict, identical on every rank: rank 0's records first, then rank 1's, ...
+    Ranks hold different numbers of records -- none at all on a rank that was dealt no scene, which must then be told
+    the IoU thresholds (`thr`).  Each rank packs its own into a float64 vector [n, C, npos (C), n x (class, score, tp
+    bits)] padded to the job's maximum (one all_reduce(MAX) of the two sizes) and ONE all_gather moves them; float32
+    scores survive the trip through float64 exactly.  device: where the collectives' tensors live (default: the CPU
+    under gloo, else the current GPU).  dist=None or not initialised => the merged records, no communication."""
+    import numpy as np
+    from .iscnet.evaluation import merge_records
+    rec = merge_records(records, thr)
+    if dist is None or not dist.is_initialized():
+        return rec
+    if device is None:
+        device = torch.device("cpu") if dist.get_backend() == "gloo" else torch.device("cuda", torch.cuda.current_device())
+    n, n_cls, n_thr = len(rec['cls']), len(rec['npos']), len(rec['thr'])
+    sizes = torch.tensor([n, n_cls], dtype=torch.int64, device=device)
+    dist.all_reduce(sizes, op=dist.ReduceOp.MAX)
+    n_max, c_max = int(sizes[0]), int(sizes[1])
+    vec = np.zeros(2 + c_max + 3 * n_max)
+    vec[0], vec[1] = n, n_cls
+    vec[2:2 + n_cls] = rec['npos']
+    body = vec[2 + c_max:].reshape(n_max, 3)
+    body[:n, 0] = rec['cls']
+    body[:n, 1] = rec['score']
+    body[:n, 2] = (rec['tp'].astype(np.int64) << np.arange(n_thr)[:, None]).sum(0)
+    mine = torch.from_numpy(vec).to(device)
+    world = dist.get_world_size()
+    out = torch.empty(world * mine.numel(), dtype=torch.float64, device=device)
+    dist.all_gather_into_tensor(out, mine)
+    out = out.view(world, -1).cpu().numpy()
+    parts = []
+    for row in out:
+        k, c = int(row[0]), int(row[1])
+        b = row[2 + c_max:].reshape(n_max, 3)[:k]
+        bits = b[:, 2].astype(np.int64)
+        parts.append({'cls': b[:, 0].astype(np.int32), 'score': b[:, 1].astype(np.float32),
+                      'tp': ((bits[None, :] >> np.arange(n_thr)[:, None]) & 1).astype(np.uint8),
+                      'npos': row[2:2 + c].astype(np.int64), 'thr': rec['thr']})
+    return merge_records(parts, rec['thr'])

@@ -58,13 +58,15 @@ def load_seeded(module, seed):
     return shapes
 
 
-def synthetic_scene(seed=10, n_raw=120000, n_points=80000, with_origin_pts=True):
+def synthetic_scene(seed=10, n_raw=120000, n_points=80000, with_origin_pts=True, return_boxes=False):
     """ScanNet-like room: 6x7x2.8 m, floor + 4 walls + 12
     cuboid 'furniture' surfaces, sigma=5 mm noise, 16 points within 0.02 m of
     the origin (exercise the FPS |p|^2 <= 1e-3 skip), height channel =
     z - percentile(z, 0.99) (demo.py:38-40), random subsample to n_points
     (with replacement when n_raw < n_points, pc_util.py:35-47).
-    Returns (n_points, 4) float32."""
+    Returns (n_points, 4) float32; with return_boxes also the 12 furniture cuboids as (12, 7) float64 [centre xyz,
+    size lwh, heading] in the scan's frame (the layout of parse_predictions' box_params) and a class id per box
+    (12,) int64 -- ground truth for an evaluation sweep.  The random stream and the points do not depend on the flag."""
     rng = np.random.default_rng(seed)
     W, L, Hh = 6.0, 7.0, 2.8
     parts = []
@@ -84,11 +86,13 @@ def synthetic_scene(seed=10, n_raw=120000, n_points=80000, with_origin_pts=True)
     n_left = n_raw - n_floor - 4 * n_wall - (16 if with_origin_pts else 0)
     n_obj = 12
     per = n_left // n_obj
+    boxes = np.zeros((n_obj, 7))
     for i in range(n_obj):
         size = rng.uniform(0.4, 1.6, 3) * np.array([1.0, 1.0, 0.7])
         ctr = np.array([rng.uniform(-W / 2 + 0.8, W / 2 - 0.8),
                         rng.uniform(-L / 2 + 0.8, L / 2 - 0.8), size[2] / 2])
         ang = rng.uniform(0, np.pi)
+        boxes[i] = np.concatenate([ctr, size, [ang]])
         n_i = per if i < n_obj - 1 else n_left - per * (n_obj - 1)
         face = rng.integers(0, 5, n_i)          # 4 sides + top
         uv = rng.random((n_i, 2)) - 0.5
@@ -118,4 +122,6 @@ def synthetic_scene(seed=10, n_raw=120000, n_points=80000, with_origin_pts=True)
     pc = np.concatenate([pts, height[:, None]], 1).astype(np.float32)
     replace = pc.shape[0] < n_points
     choice = rng.choice(pc.shape[0], n_points, replace=replace)
+    if return_boxes:
+        return np.ascontiguousarray(pc[choice]), boxes, np.arange(n_obj, dtype=np.int64) % 8
     return np.ascontiguousarray(pc[choice])
