@@ -14,81 +14,92 @@ LIB_PATH = os.environ.get("RFD_HIP_LIB") or os.path.join(_HERE, "lib", "librfd_h
 _f = C.c_void_p      # device pointers travel as integers (tensor.data_ptr())
 _i = C.c_int
 _fl = C.c_float
+_sz = C.c_size_t
 
-# name -> argtypes, exactly the prototypes of include/rfd_pointnet2.h / rfd_occ.h / rfd_chamfer.h / rfd_eval.h
-SIGNATURES = {
-    "furthest_point_sampling_kernel_wrapper": [_i, _i, _i, _f, _f, _f, _f],
-    "gather_points_kernel_wrapper": [_i, _i, _i, _i, _f, _f, _f, _f],
-    "gather_points_grad_kernel_wrapper": [_i, _i, _i, _i, _f, _f, _f, _f],
-    "query_ball_point_kernel_wrapper": [_i, _i, _i, _fl, _i, _f, _f, _f, _f],
-    "group_points_kernel_wrapper": [_i, _i, _i, _i, _i, _f, _f, _f, _f],
-    "group_points_grad_kernel_wrapper": [_i, _i, _i, _i, _i, _f, _f, _f, _f],
-    "three_nn_kernel_wrapper": [_i, _i, _i, _f, _f, _f, _f, _f],
-    "three_interpolate_kernel_wrapper": [_i, _i, _i, _i, _f, _f, _f, _f, _f],
-    "three_interpolate_grad_kernel_wrapper": [_i, _i, _i, _i, _f, _f, _f, _f, _f],
-    "rfd_group_concat": [_i, _i, _i, _i, _i, _fl, _i, _i, _f, _f, _f, _f, _f, _f, _f],
-    "rfd_furthest_point_sampling_gather": [_i, _i, _i, _f, _f, _f, _f, _f],
-    "rfd_chamfer_forward": [_i, _i, _f, _i, _f, _f, _f, _f, _f, _f],
-    "rfd_chamfer_backward": [_i, _i, _f, _i, _f, _f, _f, _f, _f, _f, _f, _f],
-    "rfd_sa_fused": [_i, _i, _i, _i, _i, _fl, _i, _f, _f, _f, _f, _i, _i, _i, _f, _f, _f, _f, _f, _f, _f, _f],
-    "rfd_occ_pack_weights": [_f, _f, C.POINTER(C.c_int), _i, _f, _f],
-    "rfd_occ_decode": [_i, _f, _f, _f, _f, _f, _f, _f, _fl, _f, _i, _f],
-    "rfd_occ_pack_weights_w8": [_f, _f, C.POINTER(C.c_int), _i, _f, _f],
-    "rfd_occ_decode_w8": [_i, _f, _f, _f, _f, _f, _f, _f, _fl, _f, _i, _f],
-    "rfd_occ_decode_scatter_w8": [_i, _f, _f, _f, _f, _f, _f, _f, _fl, _f, _f, _f, C.c_longlong, _i, _f],
-    "rfd_occ_chunk_range": [_i, _i, _i, C.POINTER(C.c_int), C.POINTER(C.c_int)],
-    "rfd_occ_chunk_range_capped": [_i, _i, _i, _i, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)],
-    "rfd_occ_set_launch_shape": [_i, _i, _i],
-    "rfd_occ_set_tail_tiles": [_i],
-    "rfd_occ_normals_w8": [_i, _f, _f, _f, _i, _f, _f, C.POINTER(C.c_int), _f, _f, _f, _f, _f, _i, _f],
-    "rfd_fps_set_timeout_ms": [_i],
-    "rfd_fps_set_geometry": [_i],
-    "rfd_test_hold_cus": [_i, _f, _i, _f],
-    "rfd_fps_test_phantom_units": [_i],
-    "rfd_make_grid_points": [_i, _fl, _fl, _fl, _f, _i, _f],
-    "rfd_mise_init": [_i, _i, _i, _f, _f, _f],
-    "rfd_mise_count": [_i, _i, _i, _f, _f, _f],
-    "rfd_mise_collect": [_i, _i, _i, _f, _f, _f, _fl, _f, _f, _f],
-    "rfd_mise_scatter": [_i, _i, _i, _f, _f, _f, _f, _f, _f, _f],
-    "rfd_mise_subdivide": [_i, _i, _i, C.c_double, _f, _f, _f, _f],
-    "rfd_mise_subdivide_active": [_i, _i, _i, C.c_double, _f, _f, _f, _f, _f],
-    "rfd_mise_subdivide_dirty": [_i, _i, _i, C.c_double, _f, _f, _f, _f, C.c_longlong, _f, _f, _f, _f, _i, _f],
-    "rfd_mise_to_dense": [_i, _i, _i, _f, _f, _f],
-    "rfd_points_in_boxes": [_i, _i, _i, _i, _f, _f, _f, _f],
-    "rfd_nms3d": [_i, _i, C.c_double, _i, _i, _f, _f, _f, _f, _f, _f],
-    "rfd_gemm_pack_w": [_i, _i, _i, _f, _f, _f],
-    "rfd_gemm_f16x3": [_i, _i, _i, _f, _i, _f, _f, _i, _f, _f, _i, _f, _i, _i, _i, _i, _i, _f, _i, _f],
-    "rfd_mc_classify": [_i, _i, _fl, C.c_double, _f, _f, _f, _f, _f],
-    "rfd_mc_emit": [_i, _i, _fl, C.c_double, _f, _f, _f, _f, _f, _f, _f, _f],
-    "rfd_mc_emit_affine": [_i, _i, _fl, C.c_double, _f, _f, _f, _f, _f, _f, _f, C.c_double, C.c_double, _f],
-    "rfd_mc_blocks": [_i],
-    "rfd_chain_pack": [_i, _f, _f, _f, _i, _i, _i, _f, _f],
-    "rfd_chain_pool": [_i, _i, _i, _i, _f, _i, _f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _f, _f],
-    "rfd_occ_fold_rows": [_i, _i, _i, _f, _f, _f, _f, _f, _f, _f, _i, _f, _f],
-    "rfd_rows3_rotate_z": [_i, _i, _f, _f, _f, _f],
-    "rfd_rows3_affine": [_i, _i, _f, _f, _f, _f],
-    "rfd_mlp_cols": [_i, _i, _i, _f, _f, _f, _f, _f, _f, _f],
-    "rfd_three_interpolate_cat": [_i, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f],
-    "rfd_chain_pack_n": [_i, _i, _f, _f, _f, _i, _i, _i, _f, _f],
-    "rfd_chain_pool_n": [_i, _i, _i, _i, _i, _f, _i, _f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _f, _f],
-    "rfd_head_pack": [_f, _f, _f, _i, _i, _i, _f, _f],
-    "rfd_head_scores": [_i, _i, _f, _i, _f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _f, _f],
-    "rfd_pos_embed": [_i, _i, _i, _f, _i, _f, _f, _i, _f, _f, _i, _f, _i, _i, _f],
-    "rfd_pos_embed_frag": [_i, _i, _i, _f, _i, _f, _f, _i, _f, _f, _i, _f, C.c_long, _i, _f],
-    "rfd_rows_to_frag": [_i, _i, _f, _i, _i, _i, _f, C.c_long, _f],
-    "rfd_frag_to_rows": [_i, _i, _f, C.c_long, _i, _f, _i, _f],
-    "rfd_gemm_f16x3_frag": [_i, _i, _i, _f, C.c_long, _f, _f, C.c_long, _f, _f, _i, _i, _i, _i, _f, _i, _f],
-    "rfd_box3d_iou": [_i, _i, _i, _f, _f, _f, _f, _f],
-    "rfd_ap_match": [_i, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _f, _f],
+# name -> (restype, argtypes[, OPTIONAL]): exactly the prototypes of include/rfd_pointnet2.h / rfd_occ.h /
+# rfd_chamfer.h / rfd_eval.h.  OPTIONAL marks the test hooks, which a deployment build (RFD_NO_TEST_HOOKS=1, build.py)
+# leaves out.
+OPTIONAL = "optional"
+ABI = {
+    "furthest_point_sampling_kernel_wrapper": (_i, [_i, _i, _i, _f, _f, _f, _f]),
+    "gather_points_kernel_wrapper": (_i, [_i, _i, _i, _i, _f, _f, _f, _f]),
+    "gather_points_grad_kernel_wrapper": (_i, [_i, _i, _i, _i, _f, _f, _f, _f]),
+    "query_ball_point_kernel_wrapper": (_i, [_i, _i, _i, _fl, _i, _f, _f, _f, _f]),
+    "group_points_kernel_wrapper": (_i, [_i, _i, _i, _i, _i, _f, _f, _f, _f]),
+    "group_points_grad_kernel_wrapper": (_i, [_i, _i, _i, _i, _i, _f, _f, _f, _f]),
+    "three_nn_kernel_wrapper": (_i, [_i, _i, _i, _f, _f, _f, _f, _f]),
+    "three_interpolate_kernel_wrapper": (_i, [_i, _i, _i, _i, _f, _f, _f, _f, _f]),
+    "three_interpolate_grad_kernel_wrapper": (_i, [_i, _i, _i, _i, _f, _f, _f, _f, _f]),
+    "rfd_group_concat": (_i, [_i, _i, _i, _i, _i, _fl, _i, _i, _f, _f, _f, _f, _f, _f, _f]),
+    "rfd_furthest_point_sampling_gather": (_i, [_i, _i, _i, _f, _f, _f, _f, _f]),
+    "rfd_chamfer_forward": (_i, [_i, _i, _f, _i, _f, _f, _f, _f, _f, _f]),
+    "rfd_chamfer_backward": (_i, [_i, _i, _f, _i, _f, _f, _f, _f, _f, _f, _f, _f]),
+    "rfd_sa_fused": (_i, [_i, _i, _i, _i, _i, _fl, _i, _f, _f, _f, _f, _i, _i, _i, _f, _f, _f, _f, _f, _f, _f, _f]),
+    "rfd_occ_pack_weights": (_i, [_f, _f, C.POINTER(C.c_int), _i, _f, _f]),
+    "rfd_occ_decode": (_i, [_i, _f, _f, _f, _f, _f, _f, _f, _fl, _f, _i, _f]),
+    "rfd_occ_pack_weights_w8": (_i, [_f, _f, C.POINTER(C.c_int), _i, _f, _f]),
+    "rfd_occ_decode_w8": (_i, [_i, _f, _f, _f, _f, _f, _f, _f, _fl, _f, _i, _f]),
+    "rfd_occ_decode_scatter_w8": (_i, [_i, _f, _f, _f, _f, _f, _f, _f, _fl, _f, _f, _f, C.c_longlong, _i, _f]),
+    "rfd_occ_chunk_range": (_i, [_i, _i, _i, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "rfd_occ_chunk_range_capped": (_i, [_i, _i, _i, _i, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "rfd_occ_set_launch_shape": (_i, [_i, _i, _i]),
+    "rfd_occ_set_tail_tiles": (_i, [_i]),
+    "rfd_occ_normals_w8": (_i, [_i, _f, _f, _f, _i, _f, _f, C.POINTER(C.c_int), _f, _f, _f, _f, _f, _i, _f]),
+    "rfd_fps_set_timeout_ms": (_i, [_i]),
+    "rfd_fps_set_geometry": (_i, [_i]),
+    "rfd_test_hold_cus": (_i, [_i, _f, _i, _f], OPTIONAL),
+    "rfd_fps_test_phantom_units": (_i, [_i], OPTIONAL),
+    "rfd_make_grid_points": (_i, [_i, _fl, _fl, _fl, _f, _i, _f]),
+    "rfd_mise_init": (_i, [_i, _i, _i, _f, _f, _f]),
+    "rfd_mise_count": (_i, [_i, _i, _i, _f, _f, _f]),
+    "rfd_mise_collect": (_i, [_i, _i, _i, _f, _f, _f, _fl, _f, _f, _f]),
+    "rfd_mise_scatter": (_i, [_i, _i, _i, _f, _f, _f, _f, _f, _f, _f]),
+    "rfd_mise_subdivide": (_i, [_i, _i, _i, C.c_double, _f, _f, _f, _f]),
+    "rfd_mise_subdivide_active": (_i, [_i, _i, _i, C.c_double, _f, _f, _f, _f, _f]),
+    "rfd_mise_subdivide_dirty": (_i, [_i, _i, _i, C.c_double, _f, _f, _f, _f, C.c_longlong, _f, _f, _f, _f, _i, _f]),
+    "rfd_mise_to_dense": (_i, [_i, _i, _i, _f, _f, _f]),
+    "rfd_points_in_boxes": (_i, [_i, _i, _i, _i, _f, _f, _f, _f]),
+    "rfd_nms3d": (_i, [_i, _i, C.c_double, _i, _i, _f, _f, _f, _f, _f, _f]),
+    "rfd_gemm_pack_w": (_i, [_i, _i, _i, _f, _f, _f]),
+    "rfd_gemm_f16x3": (_i, [_i, _i, _i, _f, _i, _f, _f, _i, _f, _f, _i, _f, _i, _i, _i, _i, _i, _f, _i, _f]),
+    "rfd_mc_classify": (_i, [_i, _i, _fl, C.c_double, _f, _f, _f, _f, _f]),
+    "rfd_mc_emit": (_i, [_i, _i, _fl, C.c_double, _f, _f, _f, _f, _f, _f, _f, _f]),
+    "rfd_mc_emit_affine": (_i, [_i, _i, _fl, C.c_double, _f, _f, _f, _f, _f, _f, _f, C.c_double, C.c_double, _f]),
+    "rfd_mc_blocks": (_i, [_i]),
+    "rfd_chain_pack": (_i, [_i, _f, _f, _f, _i, _i, _i, _f, _f]),
+    "rfd_chain_pool": (_i, [_i, _i, _i, _i, _f, _i, _f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _f, _f]),
+    "rfd_occ_fold_rows": (_i, [_i, _i, _i, _f, _f, _f, _f, _f, _f, _f, _i, _f, _f]),
+    "rfd_rows3_rotate_z": (_i, [_i, _i, _f, _f, _f, _f]),
+    "rfd_rows3_affine": (_i, [_i, _i, _f, _f, _f, _f]),
+    "rfd_mlp_cols": (_i, [_i, _i, _i, _f, _f, _f, _f, _f, _f, _f]),
+    "rfd_three_interpolate_cat": (_i, [_i, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f]),
+    "rfd_chain_pack_n": (_i, [_i, _i, _f, _f, _f, _i, _i, _i, _f, _f]),
+    "rfd_chain_pool_n": (_i, [_i, _i, _i, _i, _i, _f, _i, _f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _f, _f]),
+    "rfd_head_pack": (_i, [_f, _f, _f, _i, _i, _i, _f, _f]),
+    "rfd_head_scores": (_i, [_i, _i, _f, _i, _f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _f, _f]),
+    "rfd_pos_embed": (_i, [_i, _i, _i, _f, _i, _f, _f, _i, _f, _f, _i, _f, _i, _i, _f]),
+    "rfd_pos_embed_frag": (_i, [_i, _i, _i, _f, _i, _f, _f, _i, _f, _f, _i, _f, C.c_long, _i, _f]),
+    "rfd_rows_to_frag": (_i, [_i, _i, _f, _i, _i, _i, _f, C.c_long, _f]),
+    "rfd_frag_to_rows": (_i, [_i, _i, _f, C.c_long, _i, _f, _i, _f]),
+    "rfd_gemm_f16x3_frag": (_i, [_i, _i, _i, _f, C.c_long, _f, _f, C.c_long, _f, _f, _i, _i, _i, _i, _f, _i, _f]),
+    "rfd_box3d_iou": (_i, [_i, _i, _i, _f, _f, _f, _f, _f]),
+    "rfd_ap_match": (_i, [_i, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _f, _f]),
+    "rfd_last_error_string": (C.c_char_p, []),
+    "rfd_build_arch": (C.c_char_p, []),
+    "rfd_device_status": (_i, []),
+    "rfd_occ_packed_bytes": (_sz, []),
+    "rfd_stream_status": (_i, [_f]),
+    "rfd_release_stream": (_i, [_f]),
+    "rfd_stream_status_snapshot": (_i, [_f, _f]),
+    "rfd_mise_vstate_elems": (_sz, [_i, _i]),
+    "rfd_mise_dirty_elems": (_sz, [_i, _i]),
+    "rfd_gemm_packed_bytes": (_sz, [_i, _i]),
+    "rfd_frag_bytes": (_sz, [_i, _i]),
+    "rfd_chain_packed_bytes": (_sz, []),
+    "rfd_chain_packed_bytes_n": (_sz, [_i]),
+    "rfd_head_packed_bytes": (_sz, []),
 }
-_RESTYPES = {
-    "rfd_last_error_string": C.c_char_p,
-    "rfd_build_arch": C.c_char_p,
-    "rfd_device_status": C.c_int,
-    "rfd_occ_packed_bytes": C.c_size_t,
-}
-_INT_FNS = {"rfd_stream_status": [_f], "rfd_release_stream": [_f], "rfd_stream_status_snapshot": [_f, _f]}
-_SIZE_FNS = {"rfd_mise_vstate_elems": [_i, _i], "rfd_mise_dirty_elems": [_i, _i], "rfd_gemm_packed_bytes": [_i, _i], "rfd_frag_bytes": [_i, _i], "rfd_chain_packed_bytes": [], "rfd_chain_packed_bytes_n": [_i], "rfd_head_packed_bytes": []}
+SIGNATURES = {name: entry[1] for name, entry in ABI.items()}      # name -> argtypes (tests read it)
 
 _lib = None
 
@@ -142,29 +153,47 @@ def lib():
         # runtimes in one process cannot share device pointers or streams (the
         # second one reports "no ROCm-capable device").
         import torch  # noqa: F401
-        l = C.CDLL(LIB_PATH)
-        for name, argtypes in SIGNATURES.items():
-            fn = getattr(l, name)
-            fn.argtypes = argtypes
-            fn.restype = C.c_int
-        for name, rt in _RESTYPES.items():
-            fn = getattr(l, name)
-            fn.restype = rt
-            fn.argtypes = []
-        for name, at in _INT_FNS.items():
-            fn = getattr(l, name)
-            fn.restype = C.c_int
-            fn.argtypes = at
-        for name, at in _SIZE_FNS.items():
-            fn = getattr(l, name)
-            fn.restype = C.c_size_t
-            fn.argtypes = at
-        _lib = l
+        _lib = bind(C.CDLL(LIB_PATH))
     return _lib
 
 
+def bind(cdll):
+    """Give every ABI entry of `cdll` its restype / argtypes; -> cdll.  A required symbol that is missing raises; a
+    missing OPTIONAL one (a test hook of a deployment build) is bound to a function that raises when called."""
+    for name, (restype, argtypes, *optional) in ABI.items():
+        fn = getattr(cdll, name, None)
+        if fn is not None:
+            fn.restype, fn.argtypes = restype, argtypes
+        elif optional:
+            setattr(cdll, name, _absent_hook(name))
+        else:
+            raise RfdHipError("%s: symbol %s is missing (stale build? run `python -m rfdnet_amd.build --force`)"
+                              % (getattr(cdll, "_name", None) or LIB_PATH, name))
+    return cdll
+
+
+def _absent_hook(name):
+    def absent(*args):
+        raise RfdHipError("%s is a test hook: this library was built with RFD_NO_TEST_HOOKS" % name)
+    return absent
+
+
 def exported_symbols():
-    return sorted(list(SIGNATURES) + list(_RESTYPES) + list(_SIZE_FNS) + list(_INT_FNS))
+    return sorted(ABI)
+
+
+def ptr(t):
+    """the device pointer of an optional tensor argument"""
+    return None if t is None else t.data_ptr()
+
+
+def call(name, device, *args):
+    """The one way a host module launches: ABI entry `name` (one whose last C parameter is the stream) with `args` and
+    the current stream of `device`, on that device; a non-zero return raises, naming `name`."""
+    import torch
+    with torch.cuda.device(device):
+        rc = getattr(lib(), name)(*args, current_stream())
+    check(rc, name)
 
 
 def check(rc, what):

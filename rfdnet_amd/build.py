@@ -13,6 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_DIR = os.path.join(HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "librfd_hip.so")
+STAMP_PATH = os.path.join(LIB_DIR, "librfd_hip.stamp")      # the RFD_NO_TEST_HOOKS setting LIB_PATH was built with
 INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 
 # -ffp-contract=off: the fma placement in the point ops is part of the
@@ -34,8 +35,23 @@ def sources():
     return sorted(glob.glob(os.path.join(CSRC, "*.hip")))
 
 
+def no_test_hooks():
+    """deployment build: no rfd_test_hold_cus / rfd_fps_test_phantom_units"""
+    return os.environ.get("RFD_NO_TEST_HOOKS") == "1"
+
+
+def _stamp():
+    return "RFD_NO_TEST_HOOKS=%d\n" % no_test_hooks()
+
+
 def is_stale():
     if not os.path.exists(LIB_PATH):
+        return True
+    try:
+        with open(STAMP_PATH) as f:
+            if f.read() != _stamp():
+                return True
+    except OSError:                                     # built by something that left no stamp
         return True
     t = os.path.getmtime(LIB_PATH)
     deps = sources() + glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(INCLUDE, "*.h")) + \
@@ -49,12 +65,14 @@ def build(force=False, verbose=False):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     os.makedirs(LIB_DIR, exist_ok=True)
     flags = list(HIPCC_FLAGS)
-    if os.environ.get("RFD_NO_TEST_HOOKS") == "1":     # deployment build: no rfd_test_hold_cus / rfd_fps_test_phantom_units
+    if no_test_hooks():
         flags.append("-DRFD_NO_TEST_HOOKS")
     cmd = [hipcc] + flags + ["-o", LIB_PATH] + sources()
     if verbose:
         print(" ".join(cmd))
     subprocess.check_call(cmd)
+    with open(STAMP_PATH, "w") as f:
+        f.write(_stamp())
     return LIB_PATH
 
 

@@ -36,10 +36,8 @@ def _packed(mode, layers):
         buf = torch.empty(_lib.lib().rfd_chain_packed_bytes_n(c3), dtype=torch.uint8, device=W2.device)
         w1c = W1.contiguous() if mode == 2 else None
         w2c, w3c = W2.contiguous(), W3.contiguous()
-        with torch.cuda.device(W2.device):
-            rc = _lib.lib().rfd_chain_pack_n(mode, c3, w1c.data_ptr() if w1c is not None else None, w2c.data_ptr(),
-                                             w3c.data_ptr(), sw1, sw2, sw3, buf.data_ptr(), _lib.current_stream())
-        _lib.check(rc, "rfd_chain_pack")
+        _lib.call("rfd_chain_pack_n", W2.device, mode, c3, _lib.ptr(w1c), w2c.data_ptr(), w3c.data_ptr(), sw1, sw2, sw3,
+                  buf.data_ptr())
         torch.cuda.current_stream(W2.device).synchronize()          # w?c may be temporaries
         return (buf, sw1, sw2, sw3, (W1, W2, W3))                    # keep the keyed tensors alive
     return _lib.build_once(_cache, key, key, build, W2.device, limit=64)
@@ -62,12 +60,9 @@ def chain_pool(x, layer1, layer2, layer3, P, relu3):
     w1raw = layer1[0].contiguous() if mode == 1 else None
     b1 = layer1[1].contiguous() if mode else None
     b2, b3 = layer2[1].contiguous(), layer3[1].contiguous()
-    with torch.cuda.device(x.device):
-        rc = _lib.lib().rfd_chain_pool_n(mode, c3, M, P, d, x.data_ptr(), x.stride(0), buf.data_ptr(),
-                                       w1raw.data_ptr() if w1raw is not None else None,
-                                       b1.data_ptr() if b1 is not None else None, b2.data_ptr(), b3.data_ptr(),
-                                       int(bool(relu3)), gemm.SA, sw1, sw2, sw3, out.data_ptr(), _lib.current_stream())
-    _lib.check(rc, "rfd_chain_pool")
+    _lib.call("rfd_chain_pool_n", x.device, mode, c3, M, P, d, x.data_ptr(), x.stride(0), buf.data_ptr(),
+              _lib.ptr(w1raw), _lib.ptr(b1), b2.data_ptr(), b3.data_ptr(), int(bool(relu3)), gemm.SA, sw1, sw2, sw3,
+              out.data_ptr())
     return out
 
 
@@ -85,10 +80,8 @@ def _head_packed(Wa, Wb, Wc):
         swa, swb, swc = (occ_fold.choose_kw([w]) for w in (Wa, Wb, Wc))
         buf = torch.empty(_lib.lib().rfd_head_packed_bytes(), dtype=torch.uint8, device=Wa.device)
         wa, wb, wc = Wa.contiguous(), Wb.contiguous(), Wc.contiguous()
-        with torch.cuda.device(Wa.device):
-            rc = _lib.lib().rfd_head_pack(wa.data_ptr(), wb.data_ptr(), wc.data_ptr(), swa, swb, swc, buf.data_ptr(),
-                                          _lib.current_stream())
-        _lib.check(rc, "rfd_head_pack")
+        _lib.call("rfd_head_pack", Wa.device, wa.data_ptr(), wb.data_ptr(), wc.data_ptr(), swa, swb, swc,
+                  buf.data_ptr())
         torch.cuda.current_stream(Wa.device).synchronize()
         return (buf, swa, swb, swc, (Wa, Wb, Wc))
     return _lib.build_once(_cache, key, key, build, Wa.device, limit=64)
@@ -104,9 +97,7 @@ def head_scores(x, P, Wa, gbias, layer_b, layer_c, Wd, bd):
     buf, swa, swb, swc, _ = _head_packed(Wa, layer_b[0], layer_c[0])
     out = torch.empty(M, n_cls, dtype=torch.float32, device=x.device)
     gb, bb, bc, wd, b_d = (t.contiguous() for t in (gbias, layer_b[1], layer_c[1], Wd, bd))
-    with torch.cuda.device(x.device):
-        rc = _lib.lib().rfd_head_scores(M, P, x.data_ptr(), x.stride(0), buf.data_ptr(), gb.data_ptr(), bb.data_ptr(),
-                                        bc.data_ptr(), wd.data_ptr(), b_d.data_ptr(), n_cls, gemm.SA, swa, swb, swc,
-                                        out.data_ptr(), _lib.current_stream())
-    _lib.check(rc, "rfd_head_scores")
+    _lib.call("rfd_head_scores", x.device, M, P, x.data_ptr(), x.stride(0), buf.data_ptr(), gb.data_ptr(),
+              bb.data_ptr(), bc.data_ptr(), wd.data_ptr(), b_d.data_ptr(), n_cls, gemm.SA, swa, swb, swc,
+              out.data_ptr())
     return out

@@ -22,11 +22,8 @@ class ChamferDistanceFunction(torch.autograd.Function):
         dist2 = torch.empty(b, m, device=xyz1.device)
         idx1 = torch.empty(b, n, dtype=torch.int32, device=xyz1.device)
         idx2 = torch.empty(b, m, dtype=torch.int32, device=xyz1.device)
-        with torch.cuda.device(xyz1.device):
-            rc = _lib.lib().rfd_chamfer_forward(b, n, xyz1.data_ptr(), m, xyz2.data_ptr(), dist1.data_ptr(),
-                                                idx1.data_ptr(), dist2.data_ptr(), idx2.data_ptr(),
-                                                _lib.current_stream())
-        _lib.check(rc, "rfd_chamfer_forward")
+        _lib.call("rfd_chamfer_forward", xyz1.device, b, n, xyz1.data_ptr(), m, xyz2.data_ptr(), dist1.data_ptr(),
+                  idx1.data_ptr(), dist2.data_ptr(), idx2.data_ptr())
         ctx.save_for_backward(xyz1, xyz2, idx1, idx2)
         ctx.mark_non_differentiable(idx1, idx2)
         return dist1, dist2
@@ -40,11 +37,8 @@ class ChamferDistanceFunction(torch.autograd.Function):
         m = xyz2.size(1)
         g1 = torch.empty_like(xyz1)
         g2 = torch.empty_like(xyz2)
-        with torch.cuda.device(xyz1.device):
-            rc = _lib.lib().rfd_chamfer_backward(b, n, xyz1.data_ptr(), m, xyz2.data_ptr(), graddist1.data_ptr(),
-                                                 idx1.data_ptr(), graddist2.data_ptr(), idx2.data_ptr(),
-                                                 g1.data_ptr(), g2.data_ptr(), _lib.current_stream())
-        _lib.check(rc, "rfd_chamfer_backward")
+        _lib.call("rfd_chamfer_backward", xyz1.device, b, n, xyz1.data_ptr(), m, xyz2.data_ptr(), graddist1.data_ptr(),
+                  idx1.data_ptr(), graddist2.data_ptr(), idx2.data_ptr(), g1.data_ptr(), g2.data_ptr())
         return g1, g2
 
 
@@ -63,9 +57,6 @@ def nearest(xyz1, xyz2):
     dist2 = torch.empty(b, m, device=xyz1.device)
     idx1 = torch.empty(b, n, dtype=torch.int32, device=xyz1.device)
     idx2 = torch.empty(b, m, dtype=torch.int32, device=xyz1.device)
-    with torch.cuda.device(xyz1.device):
-        rc = _lib.lib().rfd_chamfer_forward(b, n, xyz1.data_ptr(), m, xyz2.data_ptr(), dist1.data_ptr(),
-                                            idx1.data_ptr(), dist2.data_ptr(), idx2.data_ptr(),
-                                            _lib.current_stream())
-    _lib.check(rc, "rfd_chamfer_forward")
+    _lib.call("rfd_chamfer_forward", xyz1.device, b, n, xyz1.data_ptr(), m, xyz2.data_ptr(), dist1.data_ptr(),
+              idx1.data_ptr(), dist2.data_ptr(), idx2.data_ptr())
     return dist1, idx1, dist2, idx2

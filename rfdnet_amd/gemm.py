@@ -30,9 +30,7 @@ def _packed(weight):
         N, K = w.shape
         sw = occ_fold.choose_kw([w])
         buf = torch.empty(_lib.lib().rfd_gemm_packed_bytes(N, K), dtype=torch.uint8, device=w.device)
-        with torch.cuda.device(w.device):
-            rc = _lib.lib().rfd_gemm_pack_w(N, K, sw, w.data_ptr(), buf.data_ptr(), _lib.current_stream())
-        _lib.check(rc, "rfd_gemm_pack_w")
+        _lib.call("rfd_gemm_pack_w", w.device, N, K, sw, w.data_ptr(), buf.data_ptr())
         return (buf, sw, weight)       # keep the keyed tensor alive: its address must not be reused
     return _lib.build_once(_cache, key, key, build, weight.device, limit=256)
 
@@ -54,16 +52,10 @@ def linear(x, weight, bias=None, gbias=None, rows_per_group=1, residual=None, re
     elif out is None:
         out = torch.empty(M, N, dtype=torch.float32, device=x.device)
     ldr = residual.stride(0) if residual is not None else 0
-    with torch.cuda.device(x.device):
-        rc = _lib.lib().rfd_gemm_f16x3(
-            M, N, K, x.data_ptr(), x.stride(0), packed.data_ptr(),
-            out.data_ptr() if out is not None else None, out.stride(0) if out is not None else N,
-            bias.data_ptr() if bias is not None else None,
-            gbias.data_ptr() if gbias is not None else None, int(rows_per_group),
-            residual.data_ptr() if residual is not None else None, ldr,
-            int(relu_in), int(relu_out), SA, sw, pool.data_ptr() if pool is not None else None,
-            int(pool_signed), _lib.current_stream())
-    _lib.check(rc, "rfd_gemm_f16x3")
+    _lib.call("rfd_gemm_f16x3", x.device, M, N, K, x.data_ptr(), x.stride(0), packed.data_ptr(),
+              _lib.ptr(out), out.stride(0) if out is not None else N, _lib.ptr(bias), _lib.ptr(gbias),
+              int(rows_per_group), _lib.ptr(residual), ldr, int(relu_in), int(relu_out), SA, sw, _lib.ptr(pool),
+              int(pool_signed))
     return out
 
 
@@ -117,10 +109,7 @@ def rows_to_frag(x, sa=None, relu=True, out=None):
     assert x.is_cuda and x.dtype == torch.float32 and x.stride(1) == 1
     out = frag_empty(M, Cc, x.device) if out is None else out
     ptr, stride = _frag_args(out)
-    with torch.cuda.device(x.device):
-        rc = _lib.lib().rfd_rows_to_frag(M, Cc, x.data_ptr(), x.stride(0), int(relu), int(sa), ptr, stride,
-                                         _lib.current_stream())
-    _lib.check(rc, "rfd_rows_to_frag")
+    _lib.call("rfd_rows_to_frag", x.device, M, Cc, x.data_ptr(), x.stride(0), int(relu), int(sa), ptr, stride)
     return out
 
 
@@ -130,9 +119,7 @@ def frag_to_rows(f, sa=None):
     M, Cc = f.shape[0] * 32, f.shape[1] * 32
     x = torch.empty(M, Cc, dtype=torch.float32, device=f.device)
     ptr, stride = _frag_args(f)
-    with torch.cuda.device(f.device):
-        rc = _lib.lib().rfd_frag_to_rows(M, Cc, ptr, stride, int(sa), x.data_ptr(), Cc, _lib.current_stream())
-    _lib.check(rc, "rfd_frag_to_rows")
+    _lib.call("rfd_frag_to_rows", f.device, M, Cc, ptr, stride, int(sa), x.data_ptr(), Cc)
     return x
 
 
@@ -155,12 +142,7 @@ def linear_frag(a, weight, bias=None, gbias=None, rows_per_group=1, out=None, po
         out = frag_empty(M, N, a.device)
     aptr, astride = _frag_args(a)
     cptr, cstride = _frag_args(out) if out is not None else (None, 0)
-    with torch.cuda.device(a.device):
-        rc = _lib.lib().rfd_gemm_f16x3_frag(
-            M, N, K, aptr, astride, packed.data_ptr(), cptr, cstride,
-            bias.data_ptr() if bias is not None else None, gbias.data_ptr() if gbias is not None else None,
-            int(gbias.stride(0)) if gbias is not None else 0,
-            int(rows_per_group), int(sa), sw, pool.data_ptr() if pool is not None else None, int(pool_signed),
-            _lib.current_stream())
-    _lib.check(rc, "rfd_gemm_f16x3_frag")
+    _lib.call("rfd_gemm_f16x3_frag", a.device, M, N, K, aptr, astride, packed.data_ptr(), cptr, cstride,
+              _lib.ptr(bias), _lib.ptr(gbias), int(gbias.stride(0)) if gbias is not None else 0,
+              int(rows_per_group), int(sa), sw, _lib.ptr(pool), int(pool_signed))
     return out

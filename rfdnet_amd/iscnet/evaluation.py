@@ -29,12 +29,6 @@ MAX_THRESHOLDS = 4
 LIST_GROUPS = 16384          # (scene, class) groups per launch pair of records_from_lists
 
 
-def _call(name, dev, *args):
-    with torch.cuda.device(dev):
-        rc = getattr(_lib.lib(), name)(*args, _lib.current_stream())
-    _lib.check(rc, name)
-
-
 def _thresholds(ap_iou_thresh):
     thr = tuple(float(t) for t in np.atleast_1d(np.asarray(ap_iou_thresh, dtype=np.float64)))
     if not 1 <= len(thr) <= MAX_THRESHOLDS:
@@ -68,8 +62,8 @@ def box3d_iou(pred_corners, gt_corners, with_2d=False):
     G = gt.shape[1]
     iou3d = torch.zeros(B, K, G, dtype=torch.float64, device=pred.device)
     iou2d = torch.zeros_like(iou3d) if with_2d else None
-    _call("rfd_box3d_iou", pred.device, B, K, G, pred.data_ptr(), gt.data_ptr(), iou3d.data_ptr(),
-          iou2d.data_ptr() if with_2d else None)
+    _lib.call("rfd_box3d_iou", pred.device, B, K, G, pred.data_ptr(), gt.data_ptr(), iou3d.data_ptr(),
+              _lib.ptr(iou2d))
     return (iou3d, iou2d) if with_2d else iou3d
 
 
@@ -78,8 +72,8 @@ def ap_match(iou3d, order, det_valid, gt_cls, gt_valid, thr):
     B, C, K = order.shape
     G = gt_cls.shape[1]
     tp = torch.empty(thr.numel(), B, C, K, dtype=torch.uint8, device=order.device)
-    _call("rfd_ap_match", order.device, B, C, K, G, thr.numel(), iou3d.data_ptr(), order.data_ptr(),
-          det_valid.data_ptr(), gt_cls.data_ptr(), gt_valid.data_ptr(), thr.data_ptr(), tp.data_ptr())
+    _lib.call("rfd_ap_match", order.device, B, C, K, G, thr.numel(), iou3d.data_ptr(), order.data_ptr(),
+              det_valid.data_ptr(), gt_cls.data_ptr(), gt_valid.data_ptr(), thr.data_ptr(), tp.data_ptr())
     return tp
 
 

@@ -29,12 +29,6 @@ class Mesh(object):
         self.vertex_normals = vertex_normals
 
 
-def _call(name, dev, *args):
-    with torch.cuda.device(dev):
-        rc = getattr(_lib.lib(), name)(*args, _lib.current_stream())
-    _lib.check(rc, name)
-
-
 class Generator3D(object):
     def __init__(self, model, points_batch_size=100000, threshold=0.5, refinement_step=0,
                  resolution0=16, upsampling_steps=3, with_normals=False, padding=0.1,
@@ -110,8 +104,8 @@ class Generator3D(object):
             total = nx ** 3
             tiles_per = (total + TILE - 1) // TILE
             pts = torch.empty(tiles_per * TILE, 3, dtype=torch.float32, device=dev)
-            _call("rfd_make_grid_points", dev, nx, -0.5, 0.5, float(box_size), pts.data_ptr(),
-                  tiles_per * TILE)
+            _lib.call("rfd_make_grid_points", dev, nx, -0.5, 0.5, float(box_size), pts.data_ptr(),
+                      tiles_per * TILE)
             tile_prop = torch.arange(K, dtype=torch.int32, device=dev).repeat_interleave(tiles_per)
             tile_src = torch.arange(tiles_per, dtype=torch.int32, device=dev).repeat(K)
             logits = dec.decode_tiles(pts, tile_prop, table, fc_p_w, tile_src=tile_src)
@@ -131,7 +125,7 @@ class Generator3D(object):
         counts = torch.empty(K, dtype=torch.int32, device=dev)
         # dirty-slab maps of the subdivision passes (csrc/mise.hip "dirty slabs"): two, swapped every round
         dirty = torch.zeros(2, K, lib.rfd_mise_dirty_elems(res0, depth), dtype=torch.uint8, device=dev)
-        _call("rfd_mise_init", dev, K, res0, depth, pstate.data_ptr(), vstate.data_ptr())
+        _lib.call("rfd_mise_init", dev, K, res0, depth, pstate.data_ptr(), vstate.data_ptr())
         thr = self.logit_threshold()
         n_queries, rounds = 0, 0
         per_round = []                      # real query points of each round (the rounds of generator.py:99-117)
@@ -144,7 +138,7 @@ class Generator3D(object):
                 pts, lin, tile_prop, tile_src, total = shared
                 n_tiles = tile_prop.numel()
             else:
-                _call("rfd_mise_count", dev, K, res0, depth, pstate.data_ptr(), counts.data_ptr())
+                _lib.call("rfd_mise_count", dev, K, res0, depth, pstate.data_ptr(), counts.data_ptr())
                 cnt = counts.cpu().numpy().astype(np.int64)                  # the one sync per round
                 total = int(cnt.sum())
                 if total == 0:                                               # generator.py:104
@@ -158,8 +152,8 @@ class Generator3D(object):
                 cursors = torch.zeros(K, dtype=torch.int32, device=dev)
                 pts = torch.zeros(n_tiles * TILE, 3, dtype=torch.float32, device=dev)
                 lin = torch.full((n_tiles * TILE,), -1, dtype=torch.int32, device=dev)
-                _call("rfd_mise_collect", dev, K, res0, depth, pstate.data_ptr(), offsets.data_ptr(),
-                      cursors.data_ptr(), float(box_size), pts.data_ptr(), lin.data_ptr())
+                _lib.call("rfd_mise_collect", dev, K, res0, depth, pstate.data_ptr(), offsets.data_ptr(),
+                          cursors.data_ptr(), float(box_size), pts.data_ptr(), lin.data_ptr())
             if self.round_hook is not None:           # e.g. release a host copy behind the long decode
                 self.round_hook(rounds, depth)
             if dec.can_scatter():
@@ -168,23 +162,22 @@ class Generator3D(object):
                 dec.decode_tiles(pts, tile_prop, table, fc_p_w, tile_src=tile_src, scatter=(lin, values, pstate))
             else:
                 logits = dec.decode_tiles(pts, tile_prop, table, fc_p_w, tile_src=tile_src)
-                _call("rfd_mise_scatter", dev, n_tiles, res0, depth, tile_prop.data_ptr(),
-                      tile_src.data_ptr() if tile_src is not None else None, lin.data_ptr(),
-                      logits.data_ptr(), values.data_ptr(), pstate.data_ptr())
+                _lib.call("rfd_mise_scatter", dev, n_tiles, res0, depth, tile_prop.data_ptr(),
+                          _lib.ptr(tile_src), lin.data_ptr(), logits.data_ptr(), values.data_ptr(), pstate.data_ptr())
             # proposals whose query was empty this round are finished (the reference's per-object loop has ended for
             # them, generator.py:104): the pass skips them; round 0 evaluates every proposal's lattice
             # a round that evaluated few points (the tail of the octree): only the slabs its points touch, and the ones the
             # previous pass created voxels in, are examined -- identical result, a fraction of the lattice traffic
             sparse = (not shared) and total <= K * self.sparse_round_points
-            _call("rfd_mise_subdivide_dirty", dev, K, res0, depth, float(thr), values.data_ptr(),
-                  pstate.data_ptr(), vstate.data_ptr(), None if shared else counts.data_ptr(),
-                  int(lin.numel()) if sparse else 0, lin.data_ptr() if sparse else None,
-                  tile_prop.data_ptr() if sparse else None, dirty[rounds & 1].data_ptr(),
-                  dirty[(rounds + 1) & 1].data_ptr(), int(sparse))
+            _lib.call("rfd_mise_subdivide_dirty", dev, K, res0, depth, float(thr), values.data_ptr(),
+                      pstate.data_ptr(), vstate.data_ptr(), None if shared else counts.data_ptr(),
+                      int(lin.numel()) if sparse else 0, lin.data_ptr() if sparse else None,
+                      tile_prop.data_ptr() if sparse else None, dirty[rounds & 1].data_ptr(),
+                      dirty[(rounds + 1) & 1].data_ptr(), int(sparse))
             n_queries += total
             per_round.append(total)
             rounds += 1
-        _call("rfd_mise_to_dense", dev, K, res0, depth, values.data_ptr(), pstate.data_ptr())
+        _lib.call("rfd_mise_to_dense", dev, K, res0, depth, values.data_ptr(), pstate.data_ptr())
         self.stats = {'n_queries': n_queries, 'rounds': rounds, 'per_round': per_round}
         return values.view(K, R1, R1, R1)
 
@@ -203,16 +196,16 @@ class Generator3D(object):
             ps = torch.empty(1, R1 ** 3, dtype=torch.uint8, device=dev)
             vs = torch.empty(1, _lib.lib().rfd_mise_vstate_elems(res0, depth), dtype=torch.uint8, device=dev)
             cnt = torch.empty(1, dtype=torch.int32, device=dev)
-            _call("rfd_mise_init", dev, 1, res0, depth, ps.data_ptr(), vs.data_ptr())
-            _call("rfd_mise_count", dev, 1, res0, depth, ps.data_ptr(), cnt.data_ptr())
+            _lib.call("rfd_mise_init", dev, 1, res0, depth, ps.data_ptr(), vs.data_ptr())
+            _lib.call("rfd_mise_count", dev, 1, res0, depth, ps.data_ptr(), cnt.data_ptr())
             n = int(cnt.item())
             tiles_per = (n + TILE - 1) // TILE
             pts = torch.zeros(tiles_per * TILE, 3, dtype=torch.float32, device=dev)
             lin = torch.full((tiles_per * TILE,), -1, dtype=torch.int32, device=dev)
             offsets = torch.zeros(1, dtype=torch.int32, device=dev)
             cursors = torch.zeros(1, dtype=torch.int32, device=dev)
-            _call("rfd_mise_collect", dev, 1, res0, depth, ps.data_ptr(), offsets.data_ptr(),
-                  cursors.data_ptr(), float(box_size), pts.data_ptr(), lin.data_ptr())
+            _lib.call("rfd_mise_collect", dev, 1, res0, depth, ps.data_ptr(), offsets.data_ptr(),
+                      cursors.data_ptr(), float(box_size), pts.data_ptr(), lin.data_ptr())
             torch.cuda.current_stream(dev).synchronize()       # the scratch tensors die with this frame
             tile_prop = torch.arange(K, dtype=torch.int32, device=dev).repeat_interleave(tiles_per)
             tile_src = torch.arange(tiles_per, dtype=torch.int32, device=dev).repeat(K)

@@ -7,12 +7,6 @@ import torch
 from .. import _lib
 
 
-def _call(name, dev, *args):
-    with torch.cuda.device(dev):
-        rc = getattr(_lib.lib(), name)(*args, _lib.current_stream())
-    _lib.check(rc, name)
-
-
 @torch.no_grad()
 def marching_cubes_batch(grids, threshold, pad_value=-1e6, return_flat=False, affine=None):
     """grids (K,n,n,n) f32 device tensor -> list of K (vertices (nv,3) f64,
@@ -31,8 +25,8 @@ def marching_cubes_batch(grids, threshold, pad_value=-1e6, return_flat=False, af
     nblk = _lib.lib().rfd_mc_blocks(n)
     code = torch.empty(K * per, dtype=torch.uint8, device=dev)
     sums = torch.empty(2, K * nblk, dtype=torch.int32, device=dev)          # vertices / triangles
-    _call("rfd_mc_classify", dev, K, n, float(pad_value), float(threshold), grids.data_ptr(),
-          code.data_ptr(), sums[0].data_ptr(), sums[1].data_ptr())
+    _lib.call("rfd_mc_classify", dev, K, n, float(pad_value), float(threshold), grids.data_ptr(),
+              code.data_ptr(), sums[0].data_ptr(), sums[1].data_ptr())
     # one 1-D scan over both rows (the 2-row innermost-dim scan kernel is ~70x slower)
     flat = torch.cumsum(sums.view(-1), 0, dtype=torch.int32)
     inc = flat.view(2, -1) - torch.stack([flat.new_zeros(()), flat[K * nblk - 1]]).unsqueeze(1)
@@ -47,9 +41,9 @@ def marching_cubes_batch(grids, threshold, pad_value=-1e6, return_flat=False, af
     if nv:
         vbase = torch.empty(K * per, dtype=torch.int32, device=dev)          # scratch
         va, vc = (1.0, 0.0) if affine is None else (float(affine[0]), float(affine[1]))
-        _call("rfd_mc_emit_affine", dev, K, n, float(pad_value), float(threshold), grids.data_ptr(),
-              code.data_ptr(), base[0].data_ptr(), base[1].data_ptr(), vbase.data_ptr(),
-              verts.data_ptr(), tris.data_ptr(), va, vc)
+        _lib.call("rfd_mc_emit_affine", dev, K, n, float(pad_value), float(threshold), grids.data_ptr(),
+                  code.data_ptr(), base[0].data_ptr(), base[1].data_ptr(), vbase.data_ptr(),
+                  verts.data_ptr(), tris.data_ptr(), va, vc)
     if return_flat:
         return verts[:nv], tris[:nt], vend, tend
     return [(verts[vend[k]:vend[k + 1]], tris[tend[k]:tend[k + 1]]) for k in range(K)]

@@ -147,10 +147,7 @@ class DecoderCBatchNorm(nn.Module):
             k1 = occ_fold.choose_kw([fc1])
             packed = torch.empty(_lib.lib().rfd_occ_packed_bytes(), dtype=torch.uint8, device=fc0.device)
             name = "rfd_occ_pack_weights_w8" if bwd or self.kernel == "w8" else "rfd_occ_pack_weights"
-            with torch.cuda.device(fc0.device):
-                rc = getattr(_lib.lib(), name)(fc0.data_ptr(), fc1.data_ptr(), (C.c_int * 5)(*k0), k1,
-                                               packed.data_ptr(), _lib.current_stream())
-            _lib.check(rc, name)
+            _lib.call(name, fc0.device, fc0.data_ptr(), fc1.data_ptr(), (C.c_int * 5)(*k0), k1, packed.data_ptr())
             return packed, k0, k1
         return _lib.build_once(self.__dict__, slot, key, build, self.blocks[0].fc_0.weight.device)
 
@@ -184,12 +181,9 @@ class DecoderCBatchNorm(nn.Module):
             bounds = torch.tensor([vend, gprefix], dtype=torch.int32).to(dev, non_blocking=True)
             wo = self.fc_out.weight.detach().reshape(-1).contiguous()
             kw = (C.c_int * 12)(*(list(kw0) + [kw1] + list(kb0) + [kb1]))
-            with torch.cuda.device(dev):
-                rc = _lib.lib().rfd_occ_normals_w8(
-                    gprefix[-1], verts.data_ptr(), bounds[0].data_ptr(), bounds[1].data_ptr(), K, packed.data_ptr(),
-                    packed_b.data_ptr(), kw, fc_p_w.data_ptr(), table.data_ptr(), wo.data_ptr(), normals.data_ptr(),
-                    grad.data_ptr() if grad is not None else None, self.mode, _lib.current_stream())
-            _lib.check(rc, "rfd_occ_normals_w8")
+            _lib.call("rfd_occ_normals_w8", dev, gprefix[-1], verts.data_ptr(), bounds[0].data_ptr(),
+                      bounds[1].data_ptr(), K, packed.data_ptr(), packed_b.data_ptr(), kw, fc_p_w.data_ptr(),
+                      table.data_ptr(), wo.data_ptr(), normals.data_ptr(), _lib.ptr(grad), self.mode)
         return (normals, grad) if return_grad else normals
 
     def input_grad(self, p, z, c):
@@ -263,24 +257,15 @@ class DecoderCBatchNorm(nn.Module):
             lin, values, pstate = scatter
             assert self.can_scatter() and lin.dtype == torch.int32 and lin.shape[0] == pts.shape[0]
             assert values.dtype == torch.float32 and pstate.dtype == torch.uint8 and values.is_contiguous()
-            with torch.cuda.device(pts.device):
-                rc = _lib.lib().rfd_occ_decode_scatter_w8(
-                    n_tiles, pts.data_ptr(), tile_prop.data_ptr(),
-                    tile_src.data_ptr() if tile_src is not None else None,
-                    packed.data_ptr(), fc_p_w.data_ptr(), table.data_ptr(), wo.data_ptr(), bo,
-                    lin.data_ptr(), values.data_ptr(), pstate.data_ptr(), int(values.shape[1]),
-                    self.mode if mode is None else mode, _lib.current_stream())
-            _lib.check(rc, "rfd_occ_decode_scatter_w8")
+            _lib.call("rfd_occ_decode_scatter_w8", pts.device, n_tiles, pts.data_ptr(), tile_prop.data_ptr(),
+                      _lib.ptr(tile_src), packed.data_ptr(), fc_p_w.data_ptr(), table.data_ptr(), wo.data_ptr(), bo,
+                      lin.data_ptr(), values.data_ptr(), pstate.data_ptr(), int(values.shape[1]),
+                      self.mode if mode is None else mode)
             return None
         logits = torch.empty(n_tiles * TILE, dtype=torch.float32, device=pts.device)
-        with torch.cuda.device(pts.device):
-            decode = _lib.lib().rfd_occ_decode_w8 if self.kernel == "w8" else _lib.lib().rfd_occ_decode
-            rc = decode(n_tiles, pts.data_ptr(), tile_prop.data_ptr(),
-                        tile_src.data_ptr() if tile_src is not None else None,
-                        packed.data_ptr(), fc_p_w.data_ptr(), table.data_ptr(),
-                        wo.data_ptr(), bo, logits.data_ptr(),
-                        self.mode if mode is None else mode, _lib.current_stream())
-        _lib.check(rc, "rfd_occ_decode")
+        _lib.call("rfd_occ_decode_w8" if self.kernel == "w8" else "rfd_occ_decode", pts.device, n_tiles, pts.data_ptr(),
+                  tile_prop.data_ptr(), _lib.ptr(tile_src), packed.data_ptr(), fc_p_w.data_ptr(), table.data_ptr(),
+                  wo.data_ptr(), bo, logits.data_ptr(), self.mode if mode is None else mode)
         return logits
 
     def forward(self, p, z, c, **kwargs):

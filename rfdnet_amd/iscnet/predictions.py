@@ -30,12 +30,6 @@ DEFAULT_EVAL_CONFIG = {
 }
 
 
-def _call(name, dev, *args):
-    with torch.cuda.device(dev):
-        rc = getattr(_lib.lib(), name)(*args, _lib.current_stream())
-    _lib.check(rc, name)
-
-
 def decode_boxes(end_points, dataset_config):
     """-> centre (B,K,3), size (B,K,3) [l,w,h], heading (B,K), all float64
     (ap_helper.py:149-166,176-179; scannet_config.py:43-53,71-73)."""
@@ -104,8 +98,8 @@ def parse_predictions(end_points, point_clouds, dataset_config, config=None):
         boxes = torch.cat([center, size, angle.unsqueeze(-1)], -1).contiguous()          # (B,K,7) f64
         pc = point_clouds.contiguous()
         counts = torch.empty(B, K, dtype=torch.int32, device=dev)
-        _call("rfd_points_in_boxes", dev, B, K, pc.shape[1], pc.shape[2], pc.data_ptr(),
-              boxes.data_ptr(), counts.data_ptr())
+        _lib.call("rfd_points_in_boxes", dev, B, K, pc.shape[1], pc.shape[2], pc.data_ptr(),
+                  boxes.data_ptr(), counts.data_ptr())
         nonempty = (counts >= 5).to(torch.uint8)                                         # ap_helper.py:196
 
     if not cfg['use_3d_nms']:
@@ -119,9 +113,9 @@ def parse_predictions(end_points, point_clouds, dataset_config, config=None):
     order = torch.flip(torch.argsort(obj_prob, dim=1, descending=False, stable=True), dims=[1]).int().contiguous()
     cls_i = pred_sem_cls.int().contiguous()
     valid = nonempty.contiguous()
-    _call("rfd_nms3d", dev, B, K, float(cfg['nms_iou']), int(bool(cfg['use_old_type_nms'])),
-          int(bool(cfg['cls_nms'])), aabb.data_ptr(), order.data_ptr(), cls_i.data_ptr(),
-          valid.data_ptr(), keep.data_ptr())
+    _lib.call("rfd_nms3d", dev, B, K, float(cfg['nms_iou']), int(bool(cfg['use_old_type_nms'])),
+              int(bool(cfg['cls_nms'])), aabb.data_ptr(), order.data_ptr(), cls_i.data_ptr(),
+              valid.data_ptr(), keep.data_ptr())
     parsed = {'pred_corners_3d_upright_camera': corners, 'sem_cls_probs': sem_cls_probs,
               'obj_prob': obj_prob, 'pred_sem_cls': pred_sem_cls,
               'box_params': torch.cat([center, size, angle.unsqueeze(-1)], -1),

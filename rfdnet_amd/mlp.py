@@ -45,12 +45,9 @@ def mlp_cols(x, layers):
     wts = [_transposed(W) for W, _, _ in layers]
     bs = [b.contiguous() for _, b, _ in layers]
     y = torch.empty(B, widths[-1], N, dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        rc = _lib.lib().rfd_mlp_cols(B, N, n, (C.c_int * (n + 1))(*widths), (C.c_void_p * n)(*[w.data_ptr() for w in wts]),
-                                     (C.c_void_p * n)(*[b.data_ptr() for b in bs]),
-                                     (C.c_int * n)(*[int(bool(r)) for _, _, r in layers]), x.data_ptr(), y.data_ptr(),
-                                     _lib.current_stream())
-    _lib.check(rc, "rfd_mlp_cols")
+    _lib.call("rfd_mlp_cols", x.device, B, N, n, (C.c_int * (n + 1))(*widths),
+              (C.c_void_p * n)(*[w.data_ptr() for w in wts]), (C.c_void_p * n)(*[b.data_ptr() for b in bs]),
+              (C.c_int * n)(*[int(bool(r)) for _, _, r in layers]), x.data_ptr(), y.data_ptr())
     return y
 
 
@@ -63,9 +60,6 @@ def interpolate_cat(known_feats, idx, dist2, skip):
     assert known_feats.is_cuda and known_feats.is_contiguous() and idx.is_contiguous() and dist2.is_contiguous()
     assert idx.dtype == torch.int32 and dist2.dtype == torch.float32 and (skip is None or skip.is_contiguous())
     out = torch.empty(B, c + cs, n, dtype=torch.float32, device=known_feats.device)
-    with torch.cuda.device(known_feats.device):
-        rc = _lib.lib().rfd_three_interpolate_cat(B, c, cs, m, n, known_feats.data_ptr(), idx.data_ptr(), dist2.data_ptr(),
-                                                  skip.data_ptr() if skip is not None else None, out.data_ptr(),
-                                                  _lib.current_stream())
-    _lib.check(rc, "rfd_three_interpolate_cat")
+    _lib.call("rfd_three_interpolate_cat", known_feats.device, B, c, cs, m, n, known_feats.data_ptr(), idx.data_ptr(),
+              dist2.data_ptr(), _lib.ptr(skip), out.data_ptr())
     return out

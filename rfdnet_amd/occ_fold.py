@@ -158,11 +158,9 @@ def fold_table_stacked(k, z, c):
             stride = 0
         table = torch.empty(K, TABLE_ROWS, HIDDEN, device=c.device, dtype=c.dtype)
         smul, tmul = k["smul"].reshape(-1), k["tmul"].reshape(-1)
-        with torch.cuda.device(c.device):
-            rc = _lib.lib().rfd_occ_fold_rows(K, L, HIDDEN, gb.data_ptr(), k["sqrtv"].data_ptr(), k["mean"].data_ptr(),
-                                              k["extra"].data_ptr(), smul.data_ptr(), tmul.data_ptr(), row0.data_ptr(),
-                                              stride, table.data_ptr(), _lib.current_stream())
-        _lib.check(rc, "rfd_occ_fold_rows")
+        _lib.call("rfd_occ_fold_rows", c.device, K, L, HIDDEN, gb.data_ptr(), k["sqrtv"].data_ptr(),
+                  k["mean"].data_ptr(), k["extra"].data_ptr(), smul.data_ptr(), tmul.data_ptr(), row0.data_ptr(),
+                  stride, table.data_ptr())
         return table, k["fc_p_w"]
     scale = gb[:, :L] / k["sqrtv"]
     shift = gb[:, L:] - k["mean"] * scale

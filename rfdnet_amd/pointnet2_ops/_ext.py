@@ -39,12 +39,6 @@ def _need_gpu(x):
         raise RuntimeError("CPU not supported")       # sampling.cpp:34 et al.
 
 
-def _call(fn_name, x, *args):
-    with torch.cuda.device(x.device):
-        rc = getattr(_lib.lib(), fn_name)(*args, _lib.current_stream())
-    _lib.check(rc, fn_name)
-
-
 def gather_points(points, idx):
     """(B,C,N) f32, (B,M) i32 -> (B,C,M).  sampling.cpp:15-38."""
     _chk_contig(points, "points"); _chk_contig(idx, "idx")
@@ -55,8 +49,8 @@ def gather_points(points, idx):
     B, Cc, N = points.shape
     M = idx.shape[1]
     out = torch.empty((B, Cc, M), dtype=torch.float32, device=points.device)
-    _call("gather_points_kernel_wrapper", points, B, Cc, N, M,
-          points.data_ptr(), idx.data_ptr(), out.data_ptr())
+    _lib.call("gather_points_kernel_wrapper", points.device, B, Cc, N, M,
+              points.data_ptr(), idx.data_ptr(), out.data_ptr())
     return out
 
 
@@ -69,8 +63,8 @@ def gather_points_grad(grad_out, idx, n):
     _need_gpu(grad_out)
     B, Cc, M = grad_out.shape
     out = torch.zeros((B, Cc, n), dtype=torch.float32, device=grad_out.device)
-    _call("gather_points_grad_kernel_wrapper", grad_out, B, Cc, n, M,
-          grad_out.data_ptr(), idx.data_ptr(), out.data_ptr())
+    _lib.call("gather_points_grad_kernel_wrapper", grad_out.device, B, Cc, n, M,
+              grad_out.data_ptr(), idx.data_ptr(), out.data_ptr())
     return out
 
 
@@ -81,8 +75,8 @@ def furthest_point_sampling(points, nsamples):
     B, N = points.shape[0], points.shape[1]
     out = torch.zeros((B, nsamples), dtype=torch.int32, device=points.device)
     tmp = torch.empty((B, N), dtype=torch.float32, device=points.device)
-    _call("furthest_point_sampling_kernel_wrapper", points, B, N, nsamples,
-          points.data_ptr(), tmp.data_ptr(), out.data_ptr())
+    _lib.call("furthest_point_sampling_kernel_wrapper", points.device, B, N, nsamples,
+              points.data_ptr(), tmp.data_ptr(), out.data_ptr())
     return out
 
 
@@ -97,8 +91,8 @@ def three_nn(unknowns, knows):
     m = knows.shape[1]
     idx = torch.empty((B, n, 3), dtype=torch.int32, device=unknowns.device)
     dist2 = torch.empty((B, n, 3), dtype=torch.float32, device=unknowns.device)
-    _call("three_nn_kernel_wrapper", unknowns, B, n, m, unknowns.data_ptr(),
-          knows.data_ptr(), dist2.data_ptr(), idx.data_ptr())
+    _lib.call("three_nn_kernel_wrapper", unknowns.device, B, n, m, unknowns.data_ptr(),
+              knows.data_ptr(), dist2.data_ptr(), idx.data_ptr())
     return [dist2, idx]
 
 
@@ -112,8 +106,8 @@ def three_interpolate(points, idx, weight):
     B, Cc, m = points.shape
     n = idx.shape[1]
     out = torch.empty((B, Cc, n), dtype=torch.float32, device=points.device)
-    _call("three_interpolate_kernel_wrapper", points, B, Cc, m, n,
-          points.data_ptr(), idx.data_ptr(), weight.data_ptr(), out.data_ptr())
+    _lib.call("three_interpolate_kernel_wrapper", points.device, B, Cc, m, n,
+              points.data_ptr(), idx.data_ptr(), weight.data_ptr(), out.data_ptr())
     return out
 
 
@@ -126,8 +120,8 @@ def three_interpolate_grad(grad_out, idx, weight, m):
     _need_gpu(grad_out)
     B, Cc, n = grad_out.shape
     out = torch.zeros((B, Cc, m), dtype=torch.float32, device=grad_out.device)
-    _call("three_interpolate_grad_kernel_wrapper", grad_out, B, Cc, n, m,
-          grad_out.data_ptr(), idx.data_ptr(), weight.data_ptr(), out.data_ptr())
+    _lib.call("three_interpolate_grad_kernel_wrapper", grad_out.device, B, Cc, n, m,
+              grad_out.data_ptr(), idx.data_ptr(), weight.data_ptr(), out.data_ptr())
     return out
 
 
@@ -142,8 +136,8 @@ def ball_query(new_xyz, xyz, radius, nsample):
     M = new_xyz.shape[1]
     # the kernel writes every element (zeros for empty balls): no zero-fill pass
     idx = torch.empty((B, M, nsample), dtype=torch.int32, device=new_xyz.device)
-    _call("query_ball_point_kernel_wrapper", new_xyz, B, N, M, float(radius),
-          int(nsample), new_xyz.data_ptr(), xyz.data_ptr(), idx.data_ptr())
+    _lib.call("query_ball_point_kernel_wrapper", new_xyz.device, B, N, M, float(radius),
+              int(nsample), new_xyz.data_ptr(), xyz.data_ptr(), idx.data_ptr())
     return idx
 
 
@@ -157,8 +151,8 @@ def group_points(points, idx):
     B, Cc, N = points.shape
     M, ns = idx.shape[1], idx.shape[2]
     out = torch.empty((B, Cc, M, ns), dtype=torch.float32, device=points.device)
-    _call("group_points_kernel_wrapper", points, B, Cc, N, M, ns,
-          points.data_ptr(), idx.data_ptr(), out.data_ptr())
+    _lib.call("group_points_kernel_wrapper", points.device, B, Cc, N, M, ns,
+              points.data_ptr(), idx.data_ptr(), out.data_ptr())
     return out
 
 
@@ -171,8 +165,8 @@ def group_points_grad(grad_out, idx, n):
     _need_gpu(grad_out)
     B, Cc, M, ns = grad_out.shape
     out = torch.zeros((B, Cc, n), dtype=torch.float32, device=grad_out.device)
-    _call("group_points_grad_kernel_wrapper", grad_out, B, Cc, n, M, ns,
-          grad_out.data_ptr(), idx.data_ptr(), out.data_ptr())
+    _lib.call("group_points_grad_kernel_wrapper", grad_out.device, B, Cc, n, M, ns,
+              grad_out.data_ptr(), idx.data_ptr(), out.data_ptr())
     return out
 
 
@@ -186,8 +180,8 @@ def furthest_point_sampling_gather(points, nsamples):
     out = torch.zeros((B, nsamples), dtype=torch.int32, device=points.device)
     new_xyz = torch.empty((B, nsamples, 3), dtype=torch.float32, device=points.device)
     tmp = torch.empty((B, N), dtype=torch.float32, device=points.device)
-    _call("rfd_furthest_point_sampling_gather", points, B, N, nsamples,
-          points.data_ptr(), tmp.data_ptr(), out.data_ptr(), new_xyz.data_ptr())
+    _lib.call("rfd_furthest_point_sampling_gather", points.device, B, N, nsamples,
+              points.data_ptr(), tmp.data_ptr(), out.data_ptr(), new_xyz.data_ptr())
     return out, new_xyz
 
 
@@ -200,17 +194,14 @@ def group_concat(xyz, new_xyz, features, idx, radius, normalize_xyz, use_xyz,
     B, N = xyz.shape[0], xyz.shape[1]
     M, ns = idx.shape[1], idx.shape[2]
     Cc = 0
-    fptr = None
     if features is not None:
         _chk_contig(features, "features"); _chk_float(features, "features")
         Cc = features.shape[1]
-        fptr = features.data_ptr()
     ctot = (3 if use_xyz else 0) + Cc
     out = torch.empty((B, ctot, M, ns), dtype=torch.float32, device=xyz.device)
     gx = (torch.empty((B, 3, M, ns), dtype=torch.float32, device=xyz.device)
           if ret_grouped_xyz else None)
-    _call("rfd_group_concat", xyz, B, Cc, N, M, ns, float(radius),
-          int(bool(normalize_xyz)), int(bool(use_xyz)), xyz.data_ptr(),
-          new_xyz.data_ptr(), fptr, idx.data_ptr(), out.data_ptr(),
-          gx.data_ptr() if gx is not None else None)
+    _lib.call("rfd_group_concat", xyz.device, B, Cc, N, M, ns, float(radius),
+              int(bool(normalize_xyz)), int(bool(use_xyz)), xyz.data_ptr(),
+              new_xyz.data_ptr(), _lib.ptr(features), idx.data_ptr(), out.data_ptr(), _lib.ptr(gx))
     return out, gx

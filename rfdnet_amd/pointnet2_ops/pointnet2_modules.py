@@ -240,14 +240,10 @@ class STN_Group(nn.Module):
             rows = rows.contiguous()
             cs = torch.stack([torch.cos(orientations).view(-1), torch.sin(orientations).view(-1)], 1).contiguous()
             rot = torch.empty_like(rows)
-            with torch.cuda.device(rows.device):
-                _lib.check(_lib.lib().rfd_rows3_rotate_z(B * K, P, rows.data_ptr(), cs.data_ptr(), rot.data_ptr(),
-                                                          _lib.current_stream()), "rfd_rows3_rotate_z")
+            _lib.call("rfd_rows3_rotate_z", rows.device, B * K, P, rows.data_ptr(), cs.data_ptr(), rot.data_ptr())
             A = _stn3d_affine_rows(self.stn3d, rot).contiguous()
             out = torch.empty_like(rows)
-            with torch.cuda.device(rows.device):
-                _lib.check(_lib.lib().rfd_rows3_affine(B * K, P, rot.data_ptr(), A.data_ptr(), out.data_ptr(),
-                                                        _lib.current_stream()), "rfd_rows3_affine")
+            _lib.call("rfd_rows3_affine", rows.device, B * K, P, rot.data_ptr(), A.data_ptr(), out.data_ptr())
             return out, grouped_features
         cos, sin = torch.cos(orientations).view(-1), torch.sin(orientations).view(-1)
         rot_t = torch.zeros(B * K, 3, 3, device=rows.device, dtype=rows.dtype)   # transpose of the rotation

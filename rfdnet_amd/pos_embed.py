@@ -18,11 +18,8 @@ def pos_embed(x, mask, W, bias, group, rows_per_group, out):
     N = W.shape[0]
     assert usable(x, W, out) and x.stride(1) == 1 and W.stride(1) == 1
     assert mask.is_contiguous() and mask.numel() == M and group.is_contiguous() and bias.is_contiguous()
-    with torch.cuda.device(x.device):
-        rc = _lib.lib().rfd_pos_embed(M, N, d, x.data_ptr(), x.stride(0), mask.data_ptr(), W.data_ptr(),
-                                      W.stride(0), bias.data_ptr(), group.data_ptr(), int(rows_per_group),
-                                      out.data_ptr(), out.stride(0), gemm.SA, _lib.current_stream())
-    _lib.check(rc, "rfd_pos_embed")
+    _lib.call("rfd_pos_embed", x.device, M, N, d, x.data_ptr(), x.stride(0), mask.data_ptr(), W.data_ptr(), W.stride(0),
+              bias.data_ptr(), group.data_ptr(), int(rows_per_group), out.data_ptr(), out.stride(0), gemm.SA)
     return out
 
 
@@ -40,9 +37,6 @@ def pos_embed_frag(x, mask, W, bias, group, rows_per_group, out, sa):
     assert mask.is_contiguous() and mask.numel() == M and group.is_contiguous() and bias.is_contiguous()
     assert out.shape[0] * 32 == M and out.shape[1] * 32 == N
     ptr, stride = gemm._frag_args(out)
-    with torch.cuda.device(x.device):
-        rc = _lib.lib().rfd_pos_embed_frag(M, N, d, x.data_ptr(), x.stride(0), mask.data_ptr(), W.data_ptr(),
-                                           W.stride(0), bias.data_ptr(), group.data_ptr(), int(rows_per_group),
-                                           ptr, stride, int(sa), _lib.current_stream())
-    _lib.check(rc, "rfd_pos_embed_frag")
+    _lib.call("rfd_pos_embed_frag", x.device, M, N, d, x.data_ptr(), x.stride(0), mask.data_ptr(), W.data_ptr(),
+              W.stride(0), bias.data_ptr(), group.data_ptr(), int(rows_per_group), ptr, stride, int(sa))
     return out

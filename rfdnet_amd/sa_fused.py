@@ -88,10 +88,7 @@ def forward(mlp, xyz, new_xyz, features, idx, radius, normalize_xyz):
     for t in (xyz, new_xyz, features, idx):
         assert t.is_contiguous()
     out = torch.empty(B, c3, M, dtype=torch.float32, device=xyz.device)
-    with torch.cuda.device(xyz.device):
-        rc = _lib.lib().rfd_sa_fused(B, N, M, ns, C, float(radius), int(bool(normalize_xyz)), xyz.data_ptr(),
-                                     new_xyz.data_ptr(), features.data_ptr(), idx.data_ptr(), c1, c2, c3,
-                                     w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(),
-                                     w3.data_ptr(), b3.data_ptr(), out.data_ptr(), _lib.current_stream())
-    _lib.check(rc, "rfd_sa_fused")
+    _lib.call("rfd_sa_fused", xyz.device, B, N, M, ns, C, float(radius), int(bool(normalize_xyz)), xyz.data_ptr(),
+              new_xyz.data_ptr(), features.data_ptr(), idx.data_ptr(), c1, c2, c3, w1.data_ptr(), b1.data_ptr(),
+              w2.data_ptr(), b2.data_ptr(), w3.data_ptr(), b3.data_ptr(), out.data_ptr())
     return out

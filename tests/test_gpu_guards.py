@@ -135,3 +135,23 @@ def test_decoder_logits_stay_inside_their_buffer(hip, kern):
     hip.device_status()
     assert out.shape == (3, 333) and n >= 2
     assert bad == [], bad
+
+
+@pytest.mark.parametrize("kern, entry", [("w8", "rfd_occ_decode_w8"), ("w4", "rfd_occ_decode")])
+def test_a_refused_decode_names_the_entry_point_that_ran(hip, kern, entry):
+    """mode 7 is no decoder mode: the C wrapper refuses it on the host, before any launch, and the error carries the
+    name of the entry point decode_tiles() chose for this kernel (_lib.call), not a name typed next to the call."""
+    from rfdnet_amd.iscnet.occ_decoder import TILE, DecoderCBatchNorm
+    dec = DecoderCBatchNorm(dim=3, z_dim=32, c_dim=512, hidden_size=256)
+    synthetic.load_seeded(dec, 3)
+    dec = dec.cuda().eval()
+    dec.kernel = kern
+    n_tiles = 8                                                                  # one proposal, 8 x 128 points
+    pts = torch.zeros(n_tiles * TILE, 3, device="cuda")
+    tile_prop = torch.zeros(n_tiles, dtype=torch.int32, device="cuda")
+    with torch.no_grad():
+        table, fc_p_w = dec.fold(torch.zeros(1, 32, device="cuda"), torch.zeros(1, 512, device="cuda"))
+    with pytest.raises(hip.RfdHipError) as e:
+        dec.decode_tiles(pts, tile_prop, table, fc_p_w, mode=7)
+    assert entry in str(e.value) and str(e.value).startswith(entry + " failed (hipError"), str(e.value)
+    hip.device_status()
