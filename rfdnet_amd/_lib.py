@@ -116,23 +116,57 @@ def publish(device=None):
         torch.cuda.current_stream(device).synchronize()
 
 
-def build_once(store, slot, key, build, device, limit=None):
+def sync_device(device):
+    """wait for everything queued on `device`, by any host thread on any stream (ArtefactCache's eviction)"""
+    import torch
+    torch.cuda.synchronize(device)
+
+
+def tensor_key(*tensors):
+    """(address, version, shape, device) of each tensor, None for None: a cache key for what was built from them.  The
+    address is part of it, so the tensors must live as long as the entry (ArtefactCache's `keep`)."""
+    return tuple(None if t is None else (t.data_ptr(), t._version, t.shape, t.device) for t in tensors)
+
+
+def build_once(store, slot, key, build, device):
     """store[slot] = (key, build()) unless it already holds `key`; -> the value.  The one way a shared artefact is
-    built: a miss is built under BUILD_LOCK, published on `device` (if a CUDA device) and stored in one assignment, so
-    a thread that finds it may use it on its own stream at once.  A per-object cache passes its __dict__ and a fixed
-    slot name, a multi-entry one its dict with slot = key, and `limit`: it is cleared when it holds more entries."""
+    built: a miss is built under BUILD_LOCK, published on `device` (if a CUDA device: build() need not wait for its
+    own launches) and stored in one assignment, so a thread that finds it may use it on its own stream at once.  A
+    per-object cache passes its __dict__ and a fixed slot name: the slot's old value is dropped, unsynchronised, when
+    the key changes, i.e. only when the object's parameters change, and they must not change under scenes in flight."""
     hit = store.get(slot)
     if hit is None or hit[0] != key:
         with BUILD_LOCK:
             hit = store.get(slot)
             if hit is None or hit[0] != key:
                 value = build()
-                if limit is not None and len(store) > limit:
-                    store.clear()
                 if getattr(device, "type", None) == "cuda":
                     publish(device)
                 hit = store[slot] = (key, value)
     return hit[1]
+
+
+class ArtefactCache(object):
+    """get(key, build, device, keep) -> build()'s value, built by build_once, for at most `limit` keys; `keep` (the
+    tensors the key was made of) is held with it.  A miss on a full cache evicts ONE entry, the least recently built,
+    and releases it only after sync_device() if it was built for a CUDA device: other host threads launch on streams
+    of their own and torch's allocator tracks the allocating stream only, so a device-wide wait is the one condition
+    under which no queued kernel can still read the tensor.  It costs the inference path nothing: a cache fills only
+    after hundreds of distinct weights (repeated checkpoint loads).  All of this runs under BUILD_LOCK."""
+
+    def __init__(self, limit):
+        self.limit, self.store = limit, {}
+
+    def get(self, key, build, device, keep=None):
+        def build_entry():
+            entry = (build(), keep)
+            while len(self.store) >= self.limit:
+                _, (old, old_device) = self.store.pop(next(iter(self.store)))      # dicts keep insertion order
+                if getattr(old_device, "type", None) == "cuda":
+                    sync_device(old_device)
+                del old
+            return entry, device
+        return build_once(self.store, key, key, build_entry, device)[0][0]
 
 
 class RfdHipError(RuntimeError):

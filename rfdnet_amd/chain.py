@@ -9,7 +9,7 @@ import torch
 
 from . import _lib, gemm, occ_fold
 
-_cache = {}
+_cache = _lib.ArtefactCache(64)        # the chains' and the head's weight streams
 
 
 def usable(x, P, d_in):
@@ -25,8 +25,6 @@ def usable(x, P, d_in):
 
 def _packed(mode, layers):
     (W1, _), (W2, _), (W3, _) = layers
-    key = tuple((None if w is None else (w.data_ptr(), w._version, tuple(w.shape))) for w in (W1, W2, W3)) + (mode,)
-
     def build():
         c3 = W3.shape[0]
         assert tuple(W2.shape) == (128, 64) and W3.shape[1] == 128 and c3 % 64 == 0 and 64 <= c3 <= 1024, \
@@ -38,9 +36,8 @@ def _packed(mode, layers):
         w2c, w3c = W2.contiguous(), W3.contiguous()
         _lib.call("rfd_chain_pack_n", W2.device, mode, c3, _lib.ptr(w1c), w2c.data_ptr(), w3c.data_ptr(), sw1, sw2, sw3,
                   buf.data_ptr())
-        torch.cuda.current_stream(W2.device).synchronize()          # w?c may be temporaries
-        return (buf, sw1, sw2, sw3, (W1, W2, W3))                    # keep the keyed tensors alive
-    return _lib.build_once(_cache, key, key, build, W2.device, limit=64)
+        return buf, sw1, sw2, sw3
+    return _cache.get(_lib.tensor_key(W1, W2, W3) + (mode,), build, W2.device, keep=(W1, W2, W3))
 
 
 def chain_pool(x, layer1, layer2, layer3, P, relu3):
@@ -54,7 +51,7 @@ def chain_pool(x, layer1, layer2, layer3, P, relu3):
         mode = 1 if d <= 8 else 2
         assert tuple(layer1[0].shape) == (64, d), layer1[0].shape
     assert usable(x, P, d)
-    buf, sw1, sw2, sw3, _ = _packed(mode, (layer1, layer2, layer3))
+    buf, sw1, sw2, sw3 = _packed(mode, (layer1, layer2, layer3))
     c3 = layer3[0].shape[0]
     out = torch.empty(M // P, c3, dtype=torch.float32, device=x.device)
     w1raw = layer1[0].contiguous() if mode == 1 else None
@@ -73,8 +70,6 @@ def head_usable(x, P, n_cls):
 
 
 def _head_packed(Wa, Wb, Wc):
-    key = tuple((w.data_ptr(), w._version, tuple(w.shape)) for w in (Wa, Wb, Wc)) + ("head",)
-
     def build():
         assert tuple(Wa.shape) == (512, 64) and tuple(Wb.shape) == (256, 512) and tuple(Wc.shape) == (128, 256)
         swa, swb, swc = (occ_fold.choose_kw([w]) for w in (Wa, Wb, Wc))
@@ -82,9 +77,8 @@ def _head_packed(Wa, Wb, Wc):
         wa, wb, wc = Wa.contiguous(), Wb.contiguous(), Wc.contiguous()
         _lib.call("rfd_head_pack", Wa.device, wa.data_ptr(), wb.data_ptr(), wc.data_ptr(), swa, swb, swc,
                   buf.data_ptr())
-        torch.cuda.current_stream(Wa.device).synchronize()
-        return (buf, swa, swb, swc, (Wa, Wb, Wc))
-    return _lib.build_once(_cache, key, key, build, Wa.device, limit=64)
+        return buf, swa, swb, swc
+    return _cache.get(_lib.tensor_key(Wa, Wb, Wc) + ("head",), build, Wa.device, keep=(Wa, Wb, Wc))
 
 
 def head_scores(x, P, Wa, gbias, layer_b, layer_c, Wd, bd):
@@ -94,7 +88,7 @@ def head_scores(x, P, Wa, gbias, layer_b, layer_c, Wd, bd):
     M = x.shape[0]
     n_cls = Wd.shape[0]
     assert head_usable(x, P, n_cls) and tuple(gbias.shape) == (M // P, 512)
-    buf, swa, swb, swc, _ = _head_packed(Wa, layer_b[0], layer_c[0])
+    buf, swa, swb, swc = _head_packed(Wa, layer_b[0], layer_c[0])
     out = torch.empty(M, n_cls, dtype=torch.float32, device=x.device)
     gb, bb, bc, wd, b_d = (t.contiguous() for t in (gbias, layer_b[1], layer_c[1], Wd, bd))
     _lib.call("rfd_head_scores", x.device, M, P, x.data_ptr(), x.stride(0), buf.data_ptr(), gb.data_ptr(),

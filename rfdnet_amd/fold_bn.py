@@ -15,10 +15,8 @@ def folded(layer, bn=None):
     """(W (N,K), b (N)) of `layer` (Conv1d k=1 or Linear) with `bn` folded in.
     Cached on the layer, keyed by the parameter versions."""
     w = layer.weight
-    key = (w._version, w.data_ptr(), None if layer.bias is None else layer.bias._version,
-           None if bn is None else (bn.running_mean._version, bn.running_var._version,
-                                    None if bn.weight is None else bn.weight._version,
-                                    None if bn.bias is None else bn.bias._version))
+    stats = () if bn is None else (bn.running_mean, bn.running_var, bn.weight, bn.bias)
+    key = _lib.tensor_key(w, layer.bias, *stats)
     return _lib.build_once(layer.__dict__, '_folded', key, lambda: _fold_now(layer, bn, w), w.device)
 
 

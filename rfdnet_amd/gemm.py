@@ -13,7 +13,7 @@ from . import _lib, occ_fold
 
 SA = 4            # activations scaled by 2^SA before the f16 split (|a| < 4094); lower_scale() -> SA_FALLBACK
 SA_FALLBACK = 1   # after an f16-range flag (status bit 4): |a| < 32752
-_cache = {}
+_cache = _lib.ArtefactCache(256)      # weight -> (packed stream, weight exponent)
 
 
 def usable(M, N, K, x):
@@ -23,16 +23,14 @@ def usable(M, N, K, x):
 
 def _packed(weight):
     """weight: (N,K) fp32 tensor (may be a column slice / cat built by the caller)."""
-    key = (weight.data_ptr(), weight._version, tuple(weight.shape), str(weight.device))
-
     def build():
         w = weight.detach().contiguous()
         N, K = w.shape
         sw = occ_fold.choose_kw([w])
         buf = torch.empty(_lib.lib().rfd_gemm_packed_bytes(N, K), dtype=torch.uint8, device=w.device)
         _lib.call("rfd_gemm_pack_w", w.device, N, K, sw, w.data_ptr(), buf.data_ptr())
-        return (buf, sw, weight)       # keep the keyed tensor alive: its address must not be reused
-    return _lib.build_once(_cache, key, key, build, weight.device, limit=256)
+        return buf, sw
+    return _cache.get(_lib.tensor_key(weight), build, weight.device, keep=weight)
 
 
 def linear(x, weight, bias=None, gbias=None, rows_per_group=1, residual=None, relu_in=False,
@@ -45,7 +43,7 @@ def linear(x, weight, bias=None, gbias=None, rows_per_group=1, residual=None, re
     M, K = x.shape
     N = weight.shape[0]
     assert usable(M, N, K, x)
-    packed, sw, _ = _packed(weight)
+    packed, sw = _packed(weight)
     if store is False:
         assert pool is not None, "store=False only makes sense with a pool"
         out = None
@@ -134,7 +132,7 @@ def linear_frag(a, weight, bias=None, gbias=None, rows_per_group=1, out=None, po
     sa = SA if sa is None else sa
     assert gbias is None or (gbias.stride(1) == 1 and gbias.shape[1] == N), "gbias: (groups, N) rows, row stride allowed"
     assert weight.shape[1] == K and frag_usable(M, N, K, rows_per_group if (gbias is not None or pool is not None) else 64)
-    packed, sw, _ = _packed(weight)
+    packed, sw = _packed(weight)
     if not store:
         assert pool is not None, "store=False only makes sense with a pool"
         out = None

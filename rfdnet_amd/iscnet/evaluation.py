@@ -113,13 +113,7 @@ class SceneRecords(object):
         return self._compact
 
 
-_thr_cache = {}
-
-
-def _device_thresholds(thr, dev):
-    """the thresholds as an f64 device tensor, uploaded once per (device, thresholds)"""
-    return _lib.build_once(_thr_cache, (str(dev), thr), (str(dev), thr),
-                           lambda: torch.tensor(thr, dtype=torch.float64, device=dev), dev, limit=64)
+_thr_cache = _lib.ArtefactCache(64)      # the thresholds as an f64 device tensor, uploaded once per (device, thresholds)
 
 
 def _records(pred_corners, score, valid, gt_corners, gt_cls, gt_valid, thr, timing=False):
@@ -133,7 +127,7 @@ def _records(pred_corners, score, valid, gt_corners, gt_cls, gt_valid, thr, timi
     # the global sort by confidence is the host's; within a (scene, class) only the order matters (stable, so equal
     # scores go by index -- the reference's np.argsort(-confidence) leaves the order of ties undefined)
     order = torch.argsort(score, dim=-1, descending=True, stable=True).int().contiguous()
-    thr_d = _device_thresholds(thr, dev)
+    thr_d = _thr_cache.get((str(dev), thr), lambda: torch.tensor(thr, dtype=torch.float64, device=dev), dev)
     if ev:
         ev[0].record(stream)
     iou3d = box3d_iou(pred_corners, gt_corners)

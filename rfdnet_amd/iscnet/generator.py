@@ -55,6 +55,7 @@ class Generator3D(object):
         self.sparse_round_points = int(os.environ.get('RFD_MISE_SPARSE_POINTS', 1024))     # (the variable: A/B runs only)
         self.stats = {}
         self.last_normals = None        # with_normals: the (V,3) f32 normals of the last extract_meshes(), all meshes
+        self._round0_cache = _lib.ArtefactCache(64)     # made here: the worker views of one network share it
 
     # ---- reference-shaped entry points ------------------------------------------
     def generate_mesh(self, object_features, cls_codes, return_stats=True):
@@ -186,12 +187,7 @@ class Generator3D(object):
         proposal (built once per configuration by the ordinary count / collect kernels, so it is
         bit-identical to what they would produce for every proposal) plus tile maps that make
         all K proposals read it.  Returns (pts, lin, tile_prop, tile_src, K * points)."""
-        key = (res0, depth, float(box_size), K, str(dev))
-        cache = self.__dict__.setdefault('_round0_cache', {})      # per K: a selection (NMS) changes K from scene to scene
-        c = cache.get(key)
-        if c is None:
-            if len(cache) >= 64:
-                cache.clear()
+        def build():
             R1 = (res0 << depth) + 1
             ps = torch.empty(1, R1 ** 3, dtype=torch.uint8, device=dev)
             vs = torch.empty(1, _lib.lib().rfd_mise_vstate_elems(res0, depth), dtype=torch.uint8, device=dev)
@@ -206,11 +202,10 @@ class Generator3D(object):
             cursors = torch.zeros(1, dtype=torch.int32, device=dev)
             _lib.call("rfd_mise_collect", dev, 1, res0, depth, ps.data_ptr(), offsets.data_ptr(),
                       cursors.data_ptr(), float(box_size), pts.data_ptr(), lin.data_ptr())
-            torch.cuda.current_stream(dev).synchronize()       # the scratch tensors die with this frame
             tile_prop = torch.arange(K, dtype=torch.int32, device=dev).repeat_interleave(tiles_per)
             tile_src = torch.arange(tiles_per, dtype=torch.int32, device=dev).repeat(K)
-            c = cache[key] = (key, (pts, lin, tile_prop, tile_src, K * n))
-        return c[1]
+            return pts, lin, tile_prop, tile_src, K * n
+        return self._round0_cache.get((res0, depth, float(box_size), K, str(dev)), build, dev)   # per K: NMS changes it
 
     # ---- mesh extraction ------------------------------------------------------------
     def extract_meshes(self, grids, fold=None):

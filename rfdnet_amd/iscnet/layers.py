@@ -53,14 +53,14 @@ class ResnetPointnet(nn.Module):
         net = self.pool(net, dim=1)
         return self.fc_c(self.actvn(net))
 
-    def forward_factored(self, pos_term):
+    def forward_factored(self, pos_term, cat=None):
         """Same function as forward(), evaluated without ever materialising
         cat([net, pooled]): the pooled half of every block input is constant over
         a proposal's points, so W[:, 512:] . relu(pooled) is ONE vector per
         proposal and only the 512-wide per-point half goes through the big GEMMs
         (-40 % FLOPs in blocks 1-4).  fc_0 and the shortcut share their input, so
-        their per-point halves run as one GEMM.  `pos_term` = fc_pos output
-        (B,T,2*hidden), passed in because its own input is factored by the caller."""
+        their per-point halves run as one GEMM.  `pos_term` = fc_pos output (B,T,2*hidden), passed in because its
+        own input is factored by the caller; block 0 runs in place if it is the window of `cat` = input_buffer()[0]."""
         import torch.nn.functional as F
         from .. import gemm
         h = self.block_0.size_h
@@ -91,9 +91,9 @@ class ResnetPointnet(nn.Module):
         weights = self._block_weights
 
         fuse_pool = gemm.pool_usable(M, h, 2 * h, T)
-        cat = self.__dict__.pop('_cat0', None)
-        if cat is None or cat.shape[0] != M or cat.device != x2.device or cat.data_ptr() + 4 * h != x2.data_ptr():
-            cat = torch.empty(M, 3 * h, device=x2.device, dtype=x2.dtype)    # caller did not use input_buffer()
+        assert cat is None or (cat.shape == (M, 3 * h) and cat[:, h:].data_ptr() == x2.data_ptr()), "not cat's window"
+        if cat is None:                                                      # caller did not use input_buffer()
+            cat = torch.empty(M, 3 * h, device=x2.device, dtype=x2.dtype)
             cat[:, h:] = x2
         pooled, width = None, 3 * h
         for i in range(5):
@@ -122,8 +122,8 @@ class ResnetPointnet(nn.Module):
         version, shared by the host threads."""
         h = self.block_0.size_h
         blk = getattr(self, 'block_%d' % i)
-        key = (blk.fc_0.weight._version, blk.fc_1.weight._version, blk.shortcut.weight._version,
-               blk.fc_0.weight.data_ptr())
+        from .. import _lib
+        key = _lib.tensor_key(blk.fc_0.weight, blk.fc_1.weight, blk.shortcut.weight)
 
         def build():
             w0, ws = blk.fc_0.weight.detach(), blk.shortcut.weight.detach()
@@ -134,7 +134,6 @@ class ResnetPointnet(nn.Module):
                     # both pooled-half matrices and both biases stacked: ONE small GEMM per block
                     None if wide else torch.cat([w0[:, h:], ws[:, h:]], 0).contiguous(),
                     None if wide else torch.cat([blk.fc_0.bias.detach(), blk.fc_1.bias.detach()]).contiguous())
-        from .. import _lib
         return (blk,) + _lib.build_once(self.__dict__.setdefault('_stack_cache', {}), i, key, build,
                                         blk.fc_0.weight.device)
 
@@ -184,9 +183,8 @@ class ResnetPointnet(nn.Module):
         return self.fc_c(pooled)                                             # = fc_c(relu(max over the points))
 
     def input_buffer(self, B, T, device):
-        """(B*T, 2*hidden) view for the fc_pos output that forward_factored can use in place
-        (it is the right-hand part of block 0's [hidden | input] buffer)."""
+        """Block 0's row-major [hidden | input] buffer and its (B*T, 2*hidden) input window, which the caller fills
+        with the fc_pos output and forward_factored(window, cat=buffer) uses in place: -> (buffer, window)."""
         h = self.block_0.size_h
         cat = torch.empty(B * T, 3 * h, device=device, dtype=torch.float32)
-        self.__dict__['_cat0'] = cat
-        return cat[:, h:]
+        return cat, cat[:, h:]

@@ -66,7 +66,8 @@ class ISCNet(nn.Module):
 
     def worker_view(self):
         """A second handle on THIS network for another host thread / stream: every parameter, buffer, sub-module and
-        packed-weight cache is shared (read-only at inference); only the mesh generator -- the one object that keeps
+        cache (packed weights, the generator's round-0 query lists) is shared (read-only at inference; an
+        _lib.ArtefactCache evicts safely under scenes in flight); only the mesh generator -- the one object that keeps
         per-call state (query statistics, the mesh buffers of the last call, the round hook) -- is the view's own.
         Several scenes in flight per GPU then cost one set of weights, not one per scene."""
         import copy
@@ -78,9 +79,6 @@ class ISCNet(nn.Module):
         gen.__dict__ = dict(self.completion.generator.__dict__)
         gen.model, gen.stats, gen.round_hook = comp, {}, None
         gen.__dict__.pop('last_buffers', None)
-        # the round-0 lattice cache is cleared wholesale when full; a view sharing the dict could free tensors another
-        # stream's decode still reads (torch's allocator tracks the allocating stream only): every view its own
-        gen.__dict__.pop('_round0_cache', None)
         comp.generator = gen
         view._modules['completion'] = comp
         return view

@@ -117,11 +117,6 @@ class DecoderCBatchNorm(nn.Module):
         self.check_range = True        # forward() reads the stream's status word after the launch
 
     # ---- weight stream (re-packed only when the parameters change) -----------
-    def _weights_key(self):
-        ps = [self.blocks[i].fc_0.weight for i in range(5)] + \
-             [self.blocks[i].fc_1.weight for i in range(5)]
-        return tuple((p.data_ptr(), p._version, str(p.device)) for p in ps)
-
     def packed_weights(self):
         """The decoder kernels' weight stream: -> (packed, kw0, kw1)."""
         return self._packed_stream('_packed', bwd=False)
@@ -133,7 +128,7 @@ class DecoderCBatchNorm(nn.Module):
         return self._packed_stream('_packed_bwd', bwd=True)
 
     def _packed_stream(self, slot, bwd):
-        key = self._weights_key() + (self.kernel,)
+        key = _lib.tensor_key(*(getattr(b, fc).weight for fc in ("fc_0", "fc_1") for b in self.blocks)) + (self.kernel,)
 
         def build():
             sd = {k: v.detach() for k, v in self.state_dict().items()}
@@ -202,10 +197,8 @@ class DecoderCBatchNorm(nn.Module):
 
     def _fc_out_bias(self):
         b = self.fc_out.bias
-        key = (b.data_ptr(), b._version)
-        if getattr(self, "_bo_cache", (None, None))[0] != key:
-            self._bo_cache = (key, float(b.detach().item()))   # one sync per weight load
-        return self._bo_cache[1]
+        return _lib.build_once(self.__dict__, '_fc_out_b', _lib.tensor_key(b), lambda: float(b.detach().item()),
+                               b.device)                       # one sync per weight load
 
     def fold(self, z, c):
         """Per-proposal table (K,23,256) + scaled fc_p weight for codes z, c."""
@@ -217,8 +210,7 @@ class DecoderCBatchNorm(nn.Module):
                 sd["fc_z.bias"] = torch.zeros(256, device=c.device)
             return occ_fold.fold_table(sd, z, c, kw0, kw1, ka=self.ka)
         ka = self.ka
-        key = tuple((p.data_ptr(), p._version) for p in self.parameters()) + \
-            tuple((b.data_ptr(), b._version) for b in self.buffers()) + (ka,)
+        key = _lib.tensor_key(*self.parameters(), *self.buffers()) + (ka,)
 
         def build():
             sd = {k: v.detach() for k, v in self.state_dict().items()}

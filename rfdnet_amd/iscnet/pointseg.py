@@ -181,8 +181,8 @@ class PointSeg(nn.Module):
         # head conv1 on cat([global (1024, per proposal), pointfeat (64, per point)]) + bn1
         W, b = folded(self.conv1, self.bn1)
         from .. import _lib
-        # per-point / per-proposal column halves, rebuilt when folded() returns another W (kept: its id is the key)
-        c = _lib.build_once(self.__dict__, '_head_split', id(W), lambda: (
+        # per-point / per-proposal column halves, rebuilt when folded() returns another W (kept: its address is the key)
+        c = _lib.build_once(self.__dict__, '_head_split', _lib.tensor_key(W), lambda: (
             W, W[:, 1024:].contiguous(), W[:, :1024].contiguous(), torch.zeros_like(b)), W.device)
         gbias = F.linear(g, c[2], b).contiguous()                              # (B,512): conv1's global-feature share + bias
         if chain.head_usable(pointfeat, P, self.k):

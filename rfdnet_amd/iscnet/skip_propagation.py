@@ -62,11 +62,11 @@ class SkipPropagation(nn.Module):
             pos_embed.pos_embed_frag(rows, maskf.view(-1), w, enc.fc_pos.bias, group, P, window, sa)
             codes = enc.forward_frag(cat, B * K, P, sa)
             return codes.view(B, K, -1).transpose(1, 2)
-        pos = enc.input_buffer(B * K, P, rows.device)                            # (B*K*P,2h) window of block 0's buffer
+        cat, pos = enc.input_buffer(B * K, P, rows.device)                       # (B*K*P,2h) window of block 0's buffer
         if pos_embed.usable(rows, w, pos):
             pos_embed.pos_embed(rows, maskf.view(-1), w, enc.fc_pos.bias, group, P, pos)
         else:
             tmp = F.linear(inp * maskf, w[:, :d], enc.fc_pos.bias)
             pos.copy_(tmp.addcmul_(maskf, group.unsqueeze(1)).view(B * K * P, -1))
-        codes = enc.forward_factored(pos.view(B * K, P, -1))
+        codes = enc.forward_factored(pos.view(B * K, P, -1), cat)
         return codes.view(B, K, -1).transpose(1, 2)

@@ -11,7 +11,7 @@ import torch
 
 from . import _lib
 
-_wt_cache = {}
+_wt_cache = _lib.ArtefactCache(256)
 
 
 def fits(N, widths):
@@ -26,14 +26,12 @@ def usable(x, widths):
 def _transposed(W):
     """(Cout, Cin) -> contiguous (Cin, pad4(Cout)) with zero padding (the kernel reads a lane's four consecutive
     output channels with one 16-byte load), cached per parameter version (shared by the host threads)"""
-    key = (W.data_ptr(), W._version, tuple(W.shape), str(W.device))
-
     def build():
         cout, cin = W.shape
         wt = torch.zeros(cin, (cout + 3) // 4 * 4, dtype=W.dtype, device=W.device)
         wt[:, :cout] = W.detach().t()
-        return (wt, W)                                 # keep the keyed tensor alive: its address is the key
-    return _lib.build_once(_wt_cache, key, key, build, W.device, limit=256)[0]
+        return wt
+    return _wt_cache.get(_lib.tensor_key(W), build, W.device, keep=W)
 
 
 def mlp_cols(x, layers):

@@ -52,7 +52,7 @@ def pack_layer(w, korder):
 def _packed(mlp):
     convs = [m for m in mlp if isinstance(m, torch.nn.Conv2d)]
     bns = [m for m in mlp if isinstance(m, torch.nn.BatchNorm2d)]
-    key = tuple((p.data_ptr(), p._version) for m in convs + bns for p in list(m.parameters()) + list(m.buffers()))
+    key = _lib.tensor_key(*(p for m in convs + bns for p in list(m.parameters()) + list(m.buffers())))
 
     def build():
         out = []

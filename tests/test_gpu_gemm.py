@@ -135,11 +135,31 @@ def test_skip_propagation_encoder_in_place_buffer(hip):
         plain = enc(x)
         pos = enc.fc_pos(x)
         a = enc.forward_factored(pos)
-        win = enc.input_buffer(4, 256, x.device)
+        cat, win = enc.input_buffer(4, 256, x.device)
         win.copy_(pos.view(-1, 1024))
-        b = enc.forward_factored(win.view(4, 256, 1024))
+        b = enc.forward_factored(win.view(4, 256, 1024), cat)
     assert torch.equal(a, b)
     assert (plain - a).abs().max().item() < 1e-4 * max(1.0, plain.abs().max().item())
+
+
+def test_linear_is_unchanged_by_cache_eviction_under_two_streams(hip, monkeypatch):
+    """four weights through a cache of two, the calls alternating between two streams: every miss of the second time
+    round evicts (and waits for the device), and every product is bit-equal to the one made with nothing evicted"""
+    from rfdnet_amd import _lib, gemm
+    g = torch.Generator(device="cuda").manual_seed(21)
+    x = torch.randn(128, 128, device="cuda", generator=g)                    # 128: the smallest shape usable() takes
+    ws = [torch.randn(128, 128, device="cuda", generator=g) * 0.1 for _ in range(4)]
+    want = [gemm.linear(x, w) for w in ws]                                   # the module's own cache: limit 256
+    torch.cuda.synchronize()
+    monkeypatch.setattr(gemm, "_cache", _lib.ArtefactCache(2))
+    streams, got = [torch.cuda.Stream(), torch.cuda.Stream()], []
+    for n in range(8):
+        with torch.cuda.stream(streams[(n + n // 4) % 2]):                  # second time round: the other stream
+            got.append(gemm.linear(x, ws[n % 4]))
+        assert len(gemm._cache.store) <= 2
+    torch.cuda.synchronize()
+    hip.device_status()
+    assert all(torch.equal(y, want[n % 4]) for n, y in enumerate(got))
 
 
 def test_fused_group_max_pool_signed(hip):
@@ -505,9 +525,9 @@ def test_encoder_on_frag_rows_matches_the_module(hip):
         cat, window = enc.frag_input_buffer(B, T, "cuda")
         pos_embed.pos_embed_frag(pts, mask, w, enc.fc_pos.bias, group, T, window, sa)
         got = enc.forward_frag(cat, B, T, sa)
-        pos = enc.input_buffer(B, T, "cuda")
+        rows_cat, pos = enc.input_buffer(B, T, "cuda")
         pos_embed.pos_embed(pts, mask, w, enc.fc_pos.bias, group, T, pos)
-        rows = enc.forward_factored(pos.view(B, T, -1))
+        rows = enc.forward_factored(pos.view(B, T, -1), rows_cat)
     hip.device_status()
     scale = want.abs().max().item()
     assert (got - want).abs().max().item() < 1e-4 * max(1.0, scale), (got - want).abs().max().item()

@@ -37,6 +37,28 @@ def test_mlp_cols_matches_fp64(hip, B, N, widths, relus):
             mlp.mlp_cols(x, layers)
 
 
+def test_mlp_cols_is_unchanged_by_cache_eviction_under_two_streams(hip, monkeypatch):
+    """three one-layer MLPs through a cache of two transposed weights, the calls alternating between two streams: every
+    call from the third on evicts (and waits for the device); every result is bit-equal to the one with nothing evicted"""
+    from rfdnet_amd import _lib, mlp
+    g = torch.Generator(device="cuda").manual_seed(22)
+    x = torch.randn(1, 8, 8, device="cuda", generator=g)
+    nets = [[(torch.randn(8, 8, device="cuda", generator=g), torch.randn(8, device="cuda", generator=g), True)]
+            for _ in range(3)]
+    with torch.no_grad():
+        want = [mlp.mlp_cols(x, layers) for layers in nets]                  # the module's own cache: limit 256
+        torch.cuda.synchronize()
+        monkeypatch.setattr(mlp, "_wt_cache", _lib.ArtefactCache(2))
+        streams, got = [torch.cuda.Stream(), torch.cuda.Stream()], []
+        for n in range(6):
+            with torch.cuda.stream(streams[n % 2]):                          # 3 nets, 2 streams: each net sees both
+                got.append(mlp.mlp_cols(x, nets[n % 3]))
+            assert len(mlp._wt_cache.store) <= 2
+    torch.cuda.synchronize()
+    hip.device_status()
+    assert all(torch.equal(y, want[n % 3]) for n, y in enumerate(got))
+
+
 def test_interpolate_cat_is_the_reference_expression(hip, oracle):
     """bit-equal to the torch expressions of PointnetFPModule.forward on top of the (oracle-checked) ops"""
     from rfdnet_amd import mlp

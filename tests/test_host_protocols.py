@@ -1,10 +1,13 @@
 """CPU: the two host-side protocols that let several scenes in flight share one model -- _lib.build_once (shared
-artefacts built once, published, stored in one assignment) and occ_decoder.run_with_range_fallback (the decoder's
+artefacts built once, published, stored in one assignment; _lib.ArtefactCache: bounded, evicting one entry after a device
+synchronise; _lib.tensor_key) and occ_decoder.run_with_range_fallback (the decoder's
 f16-range flag answered by a re-run at the fallback scale).  The status word, the runs and the decoder are stubs."""
 import contextlib
+import gc
 import threading
 import time
 import types
+import weakref
 
 import numpy as np
 import pytest
@@ -41,17 +44,6 @@ def test_build_once_rebuilds_on_a_changed_key_and_a_slot_keeps_one_entry():
     assert b == ["b"] and b is not a and list(store) == ["slot"] and store["slot"] == (2, b)
 
 
-def test_build_once_clears_a_multi_entry_store_above_its_limit():
-    store, cpu = {}, torch.device("cpu")
-    for k in range(4):
-        _lib.build_once(store, k, k, lambda: k, cpu, limit=3)
-    assert sorted(store) == [0, 1, 2, 3]                                       # up to limit + 1 entries
-    assert _lib.build_once(store, 2, 2, lambda: "new", cpu, limit=3) == 2      # a hit neither builds nor clears
-    assert len(store) == 4
-    assert _lib.build_once(store, 4, 4, lambda: 4, cpu, limit=3) == 4          # the next miss clears, then stores
-    assert store == {4: (4, 4)}
-
-
 def test_build_once_publishes_only_on_a_cuda_device(monkeypatch):
     published = []
     monkeypatch.setattr(_lib, "publish", published.append)
@@ -59,6 +51,116 @@ def test_build_once_publishes_only_on_a_cuda_device(monkeypatch):
     assert published == []
     _lib.build_once({}, "slot", 1, lambda: 0, torch.device("cuda", 0))      # (publish is a stub: no GPU needed)
     assert published == [torch.device("cuda", 0)]
+
+
+# ------------------------------------------------------------------------------------------------ ArtefactCache ----
+class Artefact(object):
+    """a value a weakref can watch (what a cached device tensor is to the allocator)"""
+
+    def __init__(self, k):
+        self.k = k
+
+
+@pytest.fixture
+def events(monkeypatch):
+    """-> the list that the stubs of publish / sync_device append ("publish" | "sync", device) to: no GPU needed"""
+    log = []
+    monkeypatch.setattr(_lib, "publish", lambda d: log.append(("publish", d)))
+    monkeypatch.setattr(_lib, "sync_device", lambda d: log.append(("sync", d)))
+    return log
+
+
+def test_artefact_cache_evicts_the_oldest_entry_only(events):
+    cache, cpu, built = _lib.ArtefactCache(3), torch.device("cpu"), []
+
+    def get(k):
+        return cache.get(k, lambda: built.append(k) or Artefact(k), cpu)
+    seen = []
+    for k in range(5):
+        assert get(k).k == k
+        seen.append(list(cache.store))
+    assert seen == [[0], [0, 1], [0, 1, 2], [1, 2, 3], [2, 3, 4]]              # one eviction per miss: 0, then 1
+    assert get(3).k == 3 and get(2).k == 2                                     # a hit neither builds nor evicts
+    assert built == [0, 1, 2, 3, 4] and list(cache.store) == [2, 3, 4]
+    assert get(0).k == 0 and list(cache.store) == [3, 4, 0]                    # least recently BUILT: the hit on 2 did
+    assert built == [0, 1, 2, 3, 4, 0]                                         # not save it; an evicted key is rebuilt
+    assert events == []                                                        # cpu: nothing published, nothing waited for
+
+
+def test_artefact_cache_synchronises_the_device_before_it_drops_an_evicted_value(events):
+    cache, dev, refs = _lib.ArtefactCache(2), torch.device("cuda", 0), []
+    for k in range(3):
+        if k == 2:
+            assert events == [("publish", dev)] * 2                            # below the limit: waits for nothing
+        refs.append(weakref.ref(cache.get(k, lambda: Artefact(k), dev), lambda _, k=k: events.append(("dropped", k))))
+        assert cache.get(k, lambda: None, dev) is refs[k]()                    # a hit
+    gc.collect()
+    # one wait per eviction, BEFORE the value goes, and before the new entry is published and stored
+    assert events[2:] == [("sync", dev), ("dropped", 0), ("publish", dev)] and list(cache.store) == [1, 2]
+    del events[:]
+    cache.get(3, lambda: Artefact(3), torch.device("cpu"))                     # the EVICTED entry's device decides
+    assert events == [("sync", dev), ("dropped", 1)] and refs[1]() is None and refs[2]() is not None
+
+
+def test_artefact_cache_keeps_its_key_tensors_alive(events):
+    cache, cpu = _lib.ArtefactCache(1), torch.device("cpu")
+    w = torch.zeros(4)
+    ref = weakref.ref(w)
+    cache.get(_lib.tensor_key(w), lambda: "packed", cpu, keep=w)
+    del w
+    gc.collect()
+    assert ref() is not None                              # cached under its address: it must not be given out again
+    cache.get("other", lambda: "x", cpu)
+    gc.collect()
+    assert ref() is None
+
+
+def test_artefact_cache_builds_once_for_eight_threads_released_together(events):
+    cache, built, out, go = _lib.ArtefactCache(4), [], [None] * 8, threading.Barrier(8)
+
+    def build():
+        built.append(1)
+        time.sleep(0.05)                       # the other seven threads arrive while this one builds
+        return object()
+
+    def work(i):
+        go.wait()
+        out[i] = cache.get(("k", 1), build, torch.device("cpu"))
+    ts = [threading.Thread(target=work, args=(i,)) for i in range(8)]
+    [t.start() for t in ts]
+    [t.join() for t in ts]
+    assert len(built) == 1 and all(o is out[0] for o in out) and list(cache.store) == [("k", 1)]
+
+
+def test_artefact_cache_under_eviction_hands_every_thread_its_own_value(events):
+    """eight threads, eight keys, room for four: whatever is evicted meanwhile, get() returns what ITS build() made"""
+    cache, bad, go = _lib.ArtefactCache(4), [], threading.Barrier(8)
+
+    def work(i):
+        go.wait()
+        for n in range(200):
+            k = (i + n) % 8
+            v = cache.get(k, lambda: ("made for", k), torch.device("cuda", 0), keep=k)
+            if v != ("made for", k) or len(cache.store) > 4:
+                bad.append((i, n, v, len(cache.store)))
+    ts = [threading.Thread(target=work, args=(i,)) for i in range(8)]
+    [t.start() for t in ts]
+    [t.join() for t in ts]
+    assert bad == [] and len(cache.store) == 4
+    assert all(e == (k, ((("made for", k), k), torch.device("cuda", 0))) for k, e in cache.store.items())
+
+
+def test_tensor_key():
+    a = torch.zeros(3, 2)
+    b = torch.zeros(3, 2)
+    k = _lib.tensor_key(a, None, b)
+    assert len(k) == 3 and k[1] is None and k == _lib.tensor_key(a, None, b)
+    assert k[0] == (a.data_ptr(), a._version, (3, 2), torch.device("cpu"))
+    assert k[0] != k[2]                                   # equal values at another address
+    assert _lib.tensor_key(a.view(2, 3)) != k[:1]         # the shape is part of it
+    a.add_(1)
+    assert _lib.tensor_key(a) != k[:1] and _lib.tensor_key(b) == k[2:]         # an in-place write: _version
+    assert _lib.tensor_key() == () and _lib.tensor_key(None) == (None,)
 
 
 # -------------------------------------------------------------------------------------- run_with_range_fallback ----
