@@ -172,11 +172,9 @@ int rfd_mise_to_dense(int K, int res0, int depth, float *values,
 int rfd_mc_blocks(int n);
 int rfd_mc_classify(int K, int n, float pad_value, double iso, const float *grids,
                     unsigned char *code, int *vsum, int *tsum, void *stream);
-int rfd_mc_emit(int K, int n, float pad_value, double iso, const float *grids,
-                const unsigned char *code, const int *vblock, const int *tblock,
-                int *vbase, double *verts, int *tris, void *stream);
-/* the same, storing va * vertex + vc (one fma per coordinate): Generator3D.extract_mesh's `v -= 0.5; v -= 1;
- * v /= n - 1; v = box * (v - 0.5)` (generator.py:163-168) is such a map, applied here instead of in a second pass */
+/* emit stores va * vertex + vc (one fma per coordinate; va = 1, vc = 0: the vertices as above): Generator3D.extract_mesh's
+ * `v -= 0.5; v -= 1; v /= n - 1; v = box * (v - 0.5)` (generator.py:163-168) is such a map, applied here instead of in a
+ * second pass */
 int rfd_mc_emit_affine(int K, int n, float pad_value, double iso, const float *grids,
                        const unsigned char *code, const int *vblock, const int *tblock,
                        int *vbase, double *verts, int *tris, double va, double vc, void *stream);
@@ -311,7 +309,6 @@ int rfd_rows3_affine(int G, int P, const float *rows, const float *A, float *out
  * result -- max(0, .) into a zero-initialised pool, the plain max into a -inf-initialised one with pool_signed).
  * Replaces, per ResnetBlockFC of the encoder (layers.py:5-48, 340-392), the ReLU + scale + split that every GEMM
  * re-did on its fp32 input, and the epilogue's transposition through LDS. */
-size_t rfd_frag_bytes(int M, int C);
 int rfd_rows_to_frag(int M, int C, const float *x, int ldx, int relu, int sa, void *out, long rb_stride, void *stream);
 int rfd_frag_to_rows(int M, int C, const void *in, long rb_stride, int sa, float *x, int ldx, void *stream);
 int rfd_gemm_f16x3_frag(int M, int N, int K, const void *A_frag, long a_rb_stride, const void *packed_w,
@@ -340,18 +337,12 @@ int rfd_pos_embed_frag(int M, int N, int d, const float *x, int ldx, const float
  *   [d_in -> 64, ReLU] -> 64 -> 128, ReLU -> 128 -> 1024 [, ReLU] -> max over the P points of a proposal
  * with the BatchNorms folded into W / b by the caller.  mode 1: first layer on d_in <= 8 input columns (STN3d);
  * mode 2: first layer 64 -> 64 (STNkd); mode 0: no first layer, x is the 64-wide point feature (encoder conv2/3).
- * rfd_chain_pack splits the weights (scaled by 2^sw, |w| 2^sw <= 2^14) into f16 (hi, lo) MFMA fragments:
- * rfd_chain_packed_bytes() bytes.  rfd_chain_pool: x [M][ldx] fp32 rows, P % 512 == 0, M % P == 0,
- * out [M / P][1024].  sa = activation scale exponent (status bit 4 when |activation| 2^sa leaves the f16 range). */
-size_t rfd_chain_packed_bytes(void);
-int rfd_chain_pack(int mode, const float *W1, const float *W2, const float *W3, int sw1, int sw2, int sw3,
-                   void *packed, void *stream);
-int rfd_chain_pool(int mode, int M, int P, int d_in, const float *x, int ldx, const void *packed,
-                   const float *W1raw, const float *b1, const float *b2, const float *b3, int relu3, int sa,
-                   int sw1, int sw2, int sw3, float *out, void *stream);
-/* the same chain with a last layer of c3 channels, a multiple of 64 up to 1024 (W3 [c3][128], b3 [c3], out [M / P][c3]):
- * 256 = the STN3d of STN_Group (pointnet2_modules.py:420-466: conv 3 -> 64 -> 128 -> 256 + BatchNorms + ReLU + max over
- * the group's points); rfd_chain_pack / rfd_chain_pool are the c3 = 1024 case */
+ * The last layer has c3 channels, a multiple of 64 up to 1024 (W3 [c3][128], b3 [c3], out [M / P][c3]): 1024 above, 256 =
+ * the STN3d of STN_Group (pointnet2_modules.py:420-466: conv 3 -> 64 -> 128 -> 256 + BatchNorms + ReLU + max over the
+ * group's points).
+ * rfd_chain_pack_n splits the weights (scaled by 2^sw, |w| 2^sw <= 2^14) into f16 (hi, lo) MFMA fragments:
+ * rfd_chain_packed_bytes_n(c3) bytes.  rfd_chain_pool_n: x [M][ldx] fp32 rows, P % 512 == 0, M % P == 0,
+ * out [M / P][c3].  sa = activation scale exponent (status bit 4 when |activation| 2^sa leaves the f16 range). */
 size_t rfd_chain_packed_bytes_n(int c3);
 int rfd_chain_pack_n(int mode, int c3, const float *W1, const float *W2, const float *W3, int sw1, int sw2, int sw3,
                      void *packed, void *stream);

@@ -63,11 +63,8 @@ ABI = {
     "rfd_gemm_pack_w": (_i, [_i, _i, _i, _f, _f, _f]),
     "rfd_gemm_f16x3": (_i, [_i, _i, _i, _f, _i, _f, _f, _i, _f, _f, _i, _f, _i, _i, _i, _i, _i, _f, _i, _f]),
     "rfd_mc_classify": (_i, [_i, _i, _fl, C.c_double, _f, _f, _f, _f, _f]),
-    "rfd_mc_emit": (_i, [_i, _i, _fl, C.c_double, _f, _f, _f, _f, _f, _f, _f, _f]),
     "rfd_mc_emit_affine": (_i, [_i, _i, _fl, C.c_double, _f, _f, _f, _f, _f, _f, _f, C.c_double, C.c_double, _f]),
     "rfd_mc_blocks": (_i, [_i]),
-    "rfd_chain_pack": (_i, [_i, _f, _f, _f, _i, _i, _i, _f, _f]),
-    "rfd_chain_pool": (_i, [_i, _i, _i, _i, _f, _i, _f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _f, _f]),
     "rfd_occ_fold_rows": (_i, [_i, _i, _i, _f, _f, _f, _f, _f, _f, _f, _i, _f, _f]),
     "rfd_rows3_rotate_z": (_i, [_i, _i, _f, _f, _f, _f]),
     "rfd_rows3_affine": (_i, [_i, _i, _f, _f, _f, _f]),
@@ -94,8 +91,6 @@ ABI = {
     "rfd_mise_vstate_elems": (_sz, [_i, _i]),
     "rfd_mise_dirty_elems": (_sz, [_i, _i]),
     "rfd_gemm_packed_bytes": (_sz, [_i, _i]),
-    "rfd_frag_bytes": (_sz, [_i, _i]),
-    "rfd_chain_packed_bytes": (_sz, []),
     "rfd_chain_packed_bytes_n": (_sz, [_i]),
     "rfd_head_packed_bytes": (_sz, []),
 }

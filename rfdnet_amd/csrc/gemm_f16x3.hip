@@ -1059,7 +1059,6 @@ RFD_API int rfd_gemm_f16x3(int M, int N, int K, const float *A, int lda, const v
 
 // ---- frag rows (see "Fragment-ordered split activations" above) ------------------------------------------------
 // bytes of a frag buffer of M rows x C channels (M % 32 == 0, C % 32 == 0): [M/32][C/32][4096]
-RFD_API size_t rfd_frag_bytes(int M, int C) { return (size_t)(M / 32) * (C / 32) * FRAG_BLOCK_BYTES; }
 
 // x [M][ldx] fp32 -> frag rows of relu?(x) 2^sa.  out = first block of row block 0, rb_stride = bytes between row blocks.
 RFD_API int rfd_rows_to_frag(int M, int C, const float *x, int ldx, int relu, int sa, void *out, long rb_stride,

@@ -311,7 +311,7 @@ RFD_API int rfd_mc_classify(int K, int n, float pad_value, double iso, const flo
 // f64 (padded-grid index coordinates), tris [NT][3] i32 with vertex indices LOCAL to each
 // proposal.
 // rfd_mc_emit_affine: the stored vertices are va * v + vc (what a caller would otherwise do in a second pass over the
-// 24 B / vertex buffer); rfd_mc_emit = the identity map.
+// 24 B / vertex buffer); va = 1, vc = 0 is the identity map.
 RFD_API int rfd_mc_emit_affine(int K, int n, float pad_value, double iso, const float *grids,
                                const unsigned char *code, const int *vblock, const int *tblock,
                                int *vbase, double *verts, int *tris, double va, double vc, void *stream) {
@@ -326,10 +326,4 @@ RFD_API int rfd_mc_emit_affine(int K, int n, float pad_value, double iso, const 
                      vblock, tblock, vbase, tris);
   RFD_CHECK_LAUNCH();
   return 0;
-}
-
-RFD_API int rfd_mc_emit(int K, int n, float pad_value, double iso, const float *grids,
-                        const unsigned char *code, const int *vblock, const int *tblock,
-                        int *vbase, double *verts, int *tris, void *stream) {
-  return rfd_mc_emit_affine(K, n, pad_value, iso, grids, code, vblock, tblock, vbase, verts, tris, 1.0, 0.0, stream);
 }

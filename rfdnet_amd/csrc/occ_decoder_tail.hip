@@ -13,8 +13,8 @@
 //
 // Arithmetic: every accumulator sees the SAME sequence of matrix instructions as in occ_decode8_kernel (per k-step: W_hi a_hi,
 // W_hi a_lo, W_lo a_hi; k-steps in order), the same fc_p / CBN / fc_out code around them -- the logits are bit-identical
-// (tests/test_gpu_decoder.py asserts it).  The conversion, the range watch and the fragment / S-T fetch helpers are
-// split_f16.h's, shared with occ_decoder8.hip and occ_normals.hip.
+// (tests/test_gpu_decoder.py asserts it).  The conversion, the range watch and the S / T fetch are split_f16.h's, the k-step
+// product and the weight-fragment ring occ_wave16.h's, shared with occ_normals.hip.
 //
 // Two waves of this kernel share a SIMD and nothing orders them, so one wave's prologue (fc_p) runs beside the other's matrix
 // instructions: the first build of this file returned wrong 16-point groups until the library was compiled with
@@ -22,8 +22,7 @@
 // beside another wave's v_mfma on gfx950 (profiles/r06_pk_f32_hazard.txt, tools/hazard/; tests/test_isa_audit.py keeps the
 // form out of every kernel).
 #include "common.h"
-#include "split_f16.h"
-#include "../../include/rfd_occ.h"
+#include "occ_wave16.h"
 
 int rfd_occ_tail_launch(int n_tiles, const float *pts, const int *tile_prop, const int *tile_src, const void *packed,
                         const float *fc_p_w, const float *table, const float *fc_out_w, float fc_out_b, float *logits,
@@ -32,13 +31,10 @@ int rfd_occ_tail_launch(int n_tiles, const float *pts, const int *tile_prop, con
 
 namespace {
 
-using namespace split_f16;
+using namespace occ_wave16;
 
-constexpr int H = RFD_OCC_HIDDEN;
-constexpr int NB = RFD_OCC_BLOCKS;
 constexpr int TILE = RFD_OCC_TILE;
 constexpr int ROWS = RFD_OCC_TABLE_ROWS;
-constexpr int HALF_FRAGS = 32;                 // fragments (1 KiB each) per half of the packed stream
 constexpr int DEPTH = 3;                       // k-steps of weight fragments in flight ahead of the one in use
 constexpr int SETS = DEPTH + 1;
 
@@ -83,31 +79,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
   auto half_ptr = [&](int h) { return wl + (size_t)h * HALF_FRAGS * 64; };
   unsigned amax16 = 0u;
 
-  // the weight stream, DEPTH k-steps ahead.  Every stage below is eight k-steps of ONE half and DEPTH < 8, so step k of a
-  // stage fetches step k + DEPTH of the same half or step k + DEPTH - 8 of the next stage's half; the rotation (set =
-  // step mod SETS, 8 mod SETS = 0) carries over stage boundaries and loop iterations.
-  Frag4 fs[SETS];
-  {
-    const half8 *h0 = half_ptr(0);
-    static_for<0, DEPTH>([&](auto kc) { frag_issue(fs[decltype(kc)::value], h0, decltype(kc)::value); });
-  }
-  auto fetch = [&](auto kc, const half8 *cur, const half8 *next) {
-    constexpr int ks = decltype(kc)::value;
-    __builtin_amdgcn_sched_barrier(0);           // a k-step's fetch and its matrix instructions stay one unit: the loads of step
-                                                 // k + DEPTH go out before step k's first MFMA, the only wait is for step k's set
-    if constexpr (ks + DEPTH < 8) frag_issue(fs[(ks + DEPTH) % SETS], cur, ks + DEPTH);
-    else frag_issue(fs[(ks + DEPTH) % SETS], next, ks + DEPTH - 8);
-  };
-  auto mma = [&](f32x4 &a0, f32x4 &a1, const Frag4 &f, const half8 &xh, const half8 &xl) {
-    a0 = mfma16(f.h0, xh, a0);
-    a1 = mfma16(f.h1, xh, a1);
-    if (X3) {
-      a0 = mfma16(f.h0, xl, a0);
-      a1 = mfma16(f.h1, xl, a1);
-      a0 = mfma16(f.l0, xh, a0);
-      a1 = mfma16(f.l1, xh, a1);
-    }
-  };
+  FragRing<DEPTH, SETS> ring;
+  ring.lane = 0;                                 // wl is the lane's own slot already
+  ring.prime(wl);
+  // (through a closure, as before the ring was shared: a direct call changes hipcc's register assignment)
+  auto fetch = [&](auto kc, const half8 *cur, const half8 *next) { ring.template fetch<decltype(kc)::value>(cur, next); };
 
   // ---- fc_p (+ fc_z bias): H' = (Wp p + bp + zb) 2^KH
   f32x4 Hs[16];
@@ -139,7 +115,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
         fetch(kc, cur, next);
         if constexpr (ks < 7) st_issue(st[(ks + 1) & 1], S0, T0, 32 * (ks + 1) + g4);
         act_kstep<X3>(Hs[2 * ks], Hs[2 * ks + 1], st[ks & 1], ahi[ks], alo[ks], amax16);
-        mma(acc_cur[0], acc_cur[1], fs[ks % SETS], ahi[ks], alo[ks]);
+        mma3<X3>(acc_cur[0], acc_cur[1], ring.fs[ks % SETS], ahi[ks], alo[ks]);
       });
     }
     ST sb;
@@ -160,14 +136,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
         static_for<0, 8>([&](auto kc) {
           constexpr int ks = decltype(kc)::value;
           fetch(kc, hA, hB);
-          mma(acc_next[0], acc_next[1], fs[ks % SETS], ahi[ks], alo[ks]);
+          mma3<X3>(acc_next[0], acc_next[1], ring.fs[ks % SETS], ahi[ks], alo[ks]);
         });
       }
       // ---- phase B: H'[t] += fc_1[16t.., slab mb] a2'
       static_for<0, 8>([&](auto kc) {
         constexpr int tp = decltype(kc)::value;
         fetch(kc, hB, hN);
-        mma(Hs[2 * tp], Hs[2 * tp + 1], fs[tp % SETS], bhi, blo);
+        mma3<X3>(Hs[2 * tp], Hs[2 * tp + 1], ring.fs[tp % SETS], bhi, blo);
       });
       acc_cur[0] = acc_next[0];
       acc_cur[1] = acc_next[1];

@@ -3,8 +3,8 @@
 //
 // Shape: the tail decoder's (occ_decoder_tail.hip) -- ONE wave per workgroup, 16 vertices, no LDS, no barrier, weight
 // fragments straight from L2 one k-step ahead, 16x16x32 MFMAs on (hi, lo) f16 splits (three products per k-step, fp32
-// accumulation).  The conversion, the range watch and the fragment / S-T fetch helpers are split_f16.h's, shared with
-// that file.
+// accumulation).  The conversion, the range watch and the S / T fetch are split_f16.h's, the k-step product and the
+// weight-fragment ring occ_wave16.h's, shared with that file.
 //
 // Forward pass: the decoder exactly as the tail kernel evaluates it (same table, same packed stream, same status bit 2 on an
 // activation beyond the f16 range), but nothing is kept of it except the ReLU masks of its 11 CBN layers.  In the D layout a
@@ -33,22 +33,17 @@
 // Groups of 16 vertices never span two meshes: gprefix[k] = first group of mesh k (K + 1 entries); a wave finds its mesh by
 // binary search, the last group of a mesh is masked.
 #include "common.h"
-#include "split_f16.h"
-#include "../../include/rfd_occ.h"
+#include "occ_wave16.h"
 
 namespace {
 
-using namespace split_f16;
+using namespace occ_wave16;
 
 typedef unsigned long long u64;
 
-constexpr int H = RFD_OCC_HIDDEN;
-constexpr int NB = RFD_OCC_BLOCKS;
 constexpr int ROWS = RFD_OCC_TABLE_ROWS;
-constexpr int HALF_FRAGS = 32;                 // fragments (1 KiB each) per half of a packed stream
 constexpr int DEPTH = 1;                       // k-steps of fragments in flight ahead of the one in use (2 would spill)
-constexpr int SETS = 2;                        // register sets, step mod SETS: 8 mod SETS = 0 carries the rotation over stages
-static_assert(SETS > DEPTH && 8 % SETS == 0, "fragment-set rotation");
+constexpr int SETS = 2;
 
 // per backward block j (= forward block NB - 1 - j): g_h multiplier 2^e1[j] on S1', g += multiplier 2^e0[j] on S0'
 struct Exps {
@@ -142,21 +137,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
   const float *tab = table + (size_t)prop * ROWS * H;
   unsigned amax16 = 0u;
 
-  Frag4 fs[SETS];
-  auto fetch = [&](auto kc, const half8 *cur, const half8 *next) {
-    constexpr int ks = decltype(kc)::value;
-    __builtin_amdgcn_sched_barrier(0);
-    if constexpr (ks + DEPTH < 8) frag_issue(fs[(ks + DEPTH) % SETS], cur, ks + DEPTH, lane);
-    else frag_issue(fs[(ks + DEPTH) % SETS], next, ks + DEPTH - 8, lane);
-  };
-  auto mma = [&](f32x4 &a0, f32x4 &a1, const Frag4 &f, const half8 &xh, const half8 &xl) {
-    a0 = mfma16(f.h0, xh, a0);
-    a1 = mfma16(f.h1, xh, a1);
-    a0 = mfma16(f.h0, xl, a0);
-    a1 = mfma16(f.h1, xl, a1);
-    a0 = mfma16(f.l0, xh, a0);
-    a1 = mfma16(f.l1, xh, a1);
-  };
+  FragRing<DEPTH, SETS> ring;
+  ring.lane = lane;
+  // (through a closure, as before the ring was shared: a direct call changes hipcc's register assignment)
+  auto fetch = [&](auto kc, const half8 *cur, const half8 *next) { ring.template fetch<decltype(kc)::value>(cur, next); };
 
   // ---- fc_p (+ fc_z bias): H' = (Wp p + bp + zb) 2^KH
   f32x4 Hs[16];
@@ -184,7 +168,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
   {
     const half8 *wl = packed_f;
     auto half_ptr = [&](int h) { return wl + (size_t)h * HALF_FRAGS * 64; };
-    static_for<0, DEPTH>([&](auto kc) { frag_issue(fs[decltype(kc)::value], half_ptr(0), decltype(kc)::value, lane); });
+    ring.prime(wl);
     for (int blk = 0; blk < NB; ++blk) {
       const float *S0 = tab + (1 + 4 * blk) * H, *T0 = S0 + H, *S1 = T0 + H, *T1 = S1 + H;
       u64 m0 = 0ull, m1 = 0ull;
@@ -198,7 +182,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
           fetch(kc, cur, next);
           if constexpr (ks < 7) st_issue(st[(ks + 1) & 1], S0, T0, 32 * (ks + 1) + g4);
           m0 |= (u64)act_kstep(Hs[2 * ks], Hs[2 * ks + 1], st[ks & 1], ahi[ks], alo[ks], amax16) << (8 * ks);
-          mma(acc_cur[0], acc_cur[1], fs[ks % SETS], ahi[ks], alo[ks]);
+          mma3<true>(acc_cur[0], acc_cur[1], ring.fs[ks % SETS], ahi[ks], alo[ks]);
         });
       }
       for (int mb = 0; mb < 8; ++mb) {
@@ -216,13 +200,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
           static_for<0, 8>([&](auto kc) {
             constexpr int ks = decltype(kc)::value;
             fetch(kc, hA, hB);
-            mma(acc_next[0], acc_next[1], fs[ks % SETS], ahi[ks], alo[ks]);
+            mma3<true>(acc_next[0], acc_next[1], ring.fs[ks % SETS], ahi[ks], alo[ks]);
           });
         }
         static_for<0, 8>([&](auto kc) {
           constexpr int tp = decltype(kc)::value;
           fetch(kc, hB, hN);
-          mma(Hs[2 * tp], Hs[2 * tp + 1], fs[tp % SETS], bhi, blo);
+          mma3<true>(Hs[2 * tp], Hs[2 * tp + 1], ring.fs[tp % SETS], bhi, blo);
         });
         acc_cur[0] = acc_next[0];
         acc_cur[1] = acc_next[1];
@@ -280,7 +264,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
           alo[ks] = __builtin_bit_cast(half8, u32x4{lw[0], lw[1], lw[2], lw[3]});
           Hs[2 * ks] = f32x4{0.f, 0.f, 0.f, 0.f};
           Hs[2 * ks + 1] = f32x4{0.f, 0.f, 0.f, 0.f};
-          mma(acc_cur[0], acc_cur[1], fs[ks % SETS], ahi[ks], alo[ks]);
+          mma3<true>(acc_cur[0], acc_cur[1], ring.fs[ks % SETS], ahi[ks], alo[ks]);
         });
       }
       for (int mb = 0; mb < 8; ++mb) {
@@ -298,14 +282,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
           static_for<0, 8>([&](auto kc) {
             constexpr int ks = decltype(kc)::value;
             fetch(kc, hA, hB);
-            mma(acc_next[0], acc_next[1], fs[ks % SETS], ahi[ks], alo[ks]);
+            mma3<true>(acc_next[0], acc_next[1], ring.fs[ks % SETS], ahi[ks], alo[ks]);
           });
         }
         // ---- g_a0[t] += W0^T[16t.., slab mb] g_h
         static_for<0, 8>([&](auto kc) {
           constexpr int tp = decltype(kc)::value;
           fetch(kc, hB, hN);
-          mma(Hs[2 * tp], Hs[2 * tp + 1], fs[tp % SETS], bhi, blo);
+          mma3<true>(Hs[2 * tp], Hs[2 * tp + 1], ring.fs[tp % SETS], bhi, blo);
         });
         acc_cur[0] = acc_next[0];
         acc_cur[1] = acc_next[1];

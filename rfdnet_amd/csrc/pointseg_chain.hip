@@ -527,14 +527,13 @@ static bool chain_width_ok(int c3) { return c3 >= 64 && c3 <= C3 && c3 % 64 == 0
 RFD_API size_t rfd_chain_packed_bytes_n(int c3) {
   return chain_width_ok(c3) ? (size_t)chain_pieces(c3) * PIECE + W2_BYTES + W1_BYTES : 0;
 }
-RFD_API size_t rfd_chain_packed_bytes(void) { return rfd_chain_packed_bytes_n(C3); }
 
 // W1 [64][64] (mode 2) or NULL, W2 [128][64], W3 [c3][128]: fp32, BatchNorm already folded in by the caller.
 // c3: the last layer's width, a multiple of 64 up to 1024.
 RFD_API int rfd_chain_pack_n(int mode, int c3, const float *W1, const float *W2, const float *W3, int sw1, int sw2,
                              int sw3, void *packed, void *stream) {
   if (mode < 0 || mode > 2 || !W2 || !W3 || (mode == 2 && !W1) || !chain_width_ok(c3)) {
-    rfd_set_error("rfd_chain_pack: mode / weights / width (64 .. 1024, multiple of 64)", hipErrorInvalidValue);
+    rfd_set_error("rfd_chain_pack_n: mode / weights / width (64 .. 1024, multiple of 64)", hipErrorInvalidValue);
     return (int)hipErrorInvalidValue;
   }
   const size_t total = rfd_chain_packed_bytes_n(c3) / 2;
@@ -542,10 +541,6 @@ RFD_API int rfd_chain_pack_n(int mode, int c3, const float *W1, const float *W2,
                      c3, W1, W2, W3, sw1, sw2, sw3, (_Float16 *)packed);
   RFD_CHECK_LAUNCH();
   return 0;
-}
-RFD_API int rfd_chain_pack(int mode, const float *W1, const float *W2, const float *W3, int sw1, int sw2, int sw3,
-                           void *packed, void *stream) {
-  return rfd_chain_pack_n(mode, C3, W1, W2, W3, sw1, sw2, sw3, packed, stream);
 }
 
 // x [M][ldx] fp32 rows (d_in <= 8 columns used in mode 1, 64 otherwise; 16-byte aligned rows for modes 0 / 2),
@@ -557,7 +552,7 @@ RFD_API int rfd_chain_pool_n(int mode, int c3, int M, int P, int d_in, const flo
   if (mode < 0 || mode > 2 || P <= 0 || P % 512 || M % P || (mode == 1 && (d_in < 1 || d_in > 8 || !W1raw)) ||
       (mode != 1 && (d_in != 64 || (ldx & 3) || ((uintptr_t)x & 15))) || (mode && !b1) || !b2 || !b3 || !out ||
       !chain_width_ok(c3)) {
-    rfd_set_error("rfd_chain_pool: need P % 512 == 0, M % P == 0, d_in <= 8 (mode 1) or 64 with 16-byte rows, "
+    rfd_set_error("rfd_chain_pool_n: need P % 512 == 0, M % P == 0, d_in <= 8 (mode 1) or 64 with 16-byte rows, "
                   "last width 64 .. 1024 in steps of 64", hipErrorInvalidValue);
     return (int)hipErrorInvalidValue;
   }
@@ -580,11 +575,6 @@ RFD_API int rfd_chain_pool_n(int mode, int c3, int M, int P, int d_in, const flo
   else hipLaunchKernelGGL(chain_kernel<2>, grid, block, 0, s, a);
   RFD_CHECK_LAUNCH();
   return 0;
-}
-RFD_API int rfd_chain_pool(int mode, int M, int P, int d_in, const float *x, int ldx, const void *packed,
-                           const float *W1raw, const float *b1, const float *b2, const float *b3, int relu3, int sa,
-                           int sw1, int sw2, int sw3, float *out, void *stream) {
-  return rfd_chain_pool_n(mode, C3, M, P, d_in, x, ldx, packed, W1raw, b1, b2, b3, relu3, sa, sw1, sw2, sw3, out, stream);
 }
 
 RFD_API size_t rfd_head_packed_bytes(void) { return (size_t)H_PIECES * HPIECE; }

@@ -8,7 +8,8 @@
 //
 // Everything here is __forceinline__: a kernel that uses a helper compiles to the instruction stream it had with its
 // own copy (tests/test_isa_audit.py pins occ_decoder8.hip's).  A source opens its anonymous namespace with
-// `using namespace split_f16;`.
+// `using namespace split_f16;`.  occ_wave16.h builds on this header: the k-step product and the weight-fragment ring of
+// the one-wave decoder kernels (occ_decoder_tail.hip, occ_normals.hip).
 #pragma once
 #include <type_traits>
 
@@ -79,7 +80,7 @@ __host__ __device__ __forceinline__ _Float16 weight_half(float w, bool want_lo) 
   return want_lo ? lo : hi;
 }
 
-// ---- operand streams of the one-wave 16x16x32 kernels (occ_decoder_tail.hip, occ_normals.hip) ------------------------
+// ---- operand streams of the 16x16x32 decoder kernels; the one-wave kernels' fragment ring is occ_wave16.h's -----------
 template <int I, int N, class F>
 __device__ __forceinline__ void static_for(F &&f) {
   if constexpr (I < N) {
@@ -103,15 +104,5 @@ __device__ __forceinline__ void st_issue(ST &d, const float *S, const float *T, 
 struct Frag4 {
   half8 h0, l0, h1, l1;
 };
-// k-step ks of a half of the packed stream: fragments 4 ks .. 4 ks + 3, 4 KiB in one piece.  A wave-uniform half_base
-// takes the lane's offset here, added last (one scalar base per half, one lane offset for all of them); a half_base that
-// already points at the lane's slot leaves it 0.
-__device__ __forceinline__ void frag_issue(Frag4 &d, const half8 *half_base, int ks, int lane = 0) {
-  const half8 *w = half_base + ks * 256 + lane;
-  d.h0 = w[0];
-  d.l0 = w[64];
-  d.h1 = w[128];
-  d.l1 = w[192];
-}
 
 }  // namespace split_f16

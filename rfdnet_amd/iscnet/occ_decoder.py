@@ -1,6 +1,8 @@
 """DecoderCBatchNorm with the reference's constructor, forward signature and
 state_dict keys (models/iscnet/modules/occ_decoder.py:72-123, layers.py:51-107,
-193-242), evaluated by ONE fused HIP kernel (csrc/occ_decoder.hip).
+193-242), evaluated by ONE fused HIP kernel: csrc/occ_decoder8.hip by default
+(launches of few tiles: csrc/occ_decoder_tail.hip; csrc/occ_decoder.hip, the
+four-wave kernel, is kept as the independent cross-check).
 
 state_dict keys (verified against the reference class by
 tests/golden/make_fixtures.py):  fc_p.{weight(256,3,1),bias}, fc_z.{weight
