@@ -85,6 +85,47 @@ def test_interpolate_cat_is_the_reference_expression(hip, oracle):
     assert torch.equal(got[:, c:], skip) and torch.equal(got_noskip, got[:, :c])
 
 
+@pytest.mark.parametrize("m", [1, 2, 3])
+def test_interpolate_cat_with_fewer_than_three_known_points_and_coincident_ones(hip, m):
+    """three_nn leaves dist2 = inf, idx = 0 in the slots it cannot fill (m = 1, 2): sqrt(inf) = inf, the weight is
+    1 / (inf + 1e-8) / norm = 0 and the slot contributes 0 * feats[0].  m = 3: three coincident known points on top of
+    an unknown -- distances (0, 0, 0) there, (d, d, d) elsewhere, so the three weights are equal.  Against the torch
+    expressions of PointnetFPModule.forward, finite everywhere."""
+    from rfdnet_amd import mlp
+    from rfdnet_amd.pointnet2_ops import _ext, pointnet2_utils
+    g = torch.Generator(device="cuda").manual_seed(40 + m)
+    B, n, c, cs = 2, 300, 5, 3
+    unknown = torch.rand(B, n, 3, device="cuda", generator=g) * 4
+    if m == 3:
+        known = unknown[:, 17:18].expand(B, 3, 3).contiguous()
+    else:
+        known = (torch.rand(B, m, 3, device="cuda", generator=g) * 4).contiguous()
+        known[:, 0] = unknown[:, 17]                            # an exact coincidence: dist 0
+    feats = torch.randn(B, c, m, device="cuda", generator=g)
+    skip = torch.randn(B, cs, n, device="cuda", generator=g)
+    with torch.no_grad():
+        dist, idx = pointnet2_utils.three_nn(unknown, known)
+        dist_recip = 1.0 / (dist + 1e-8)
+        weight = dist_recip / torch.sum(dist_recip, dim=2, keepdim=True)
+        want = torch.cat([pointnet2_utils.three_interpolate(feats, idx, weight), skip], dim=1)
+        dist2, idx2 = _ext.three_nn(unknown, known)
+        got = mlp.interpolate_cat(feats, idx2, dist2, skip)
+    hip.device_status()
+    assert torch.equal(idx, idx2)
+    if m < 3:
+        assert torch.isinf(dist2[:, :, m:]).all() and (dist2[:, :, m:] > 0).all() and torch.isfinite(dist2[:, :, :m]).all()
+        assert (idx2[:, :, m:] == 0).all() and (weight[:, :, m:] == 0).all()
+    else:
+        assert (dist2[:, 17] == 0).all() and torch.equal(idx2[:, 17].cpu(), torch.tensor([[0, 1, 2]] * B, dtype=torch.int32))
+        assert (weight[:, :, 0] == weight[:, :, 1]).all() and (weight[:, :, 1] == weight[:, :, 2]).all()
+    assert torch.isfinite(got).all() and torch.isfinite(want).all()
+    d = (got - want).abs().max().item()
+    assert d <= 1e-6 * want.abs().max().item(), d
+    assert torch.equal(got[:, c:], skip)
+    if m == 1:                                                  # one known point: its features, whatever the distance
+        assert (got[:, :c] - feats.expand(B, c, n)).abs().max().item() <= 1e-6 * feats.abs().max().item()
+
+
 def test_fp_vote_proposal_modules_fused_against_their_torch_paths(hip):
     """the three modules at inference (fused) against the same modules' torch composition (what runs under autograd)"""
     from rfdnet_amd.iscnet.config import Config

@@ -104,3 +104,20 @@ def test_oracle_iso_level_convention_and_midpoint():
     v, t = oracle.marching_cubes(g, 0.0)
     assert len(v) == 6 and len(t) == 8
     assert np.allclose(np.sort(np.abs(v - 1).sum(1)), 0.5)
+
+
+@pytest.mark.parametrize("iso", [np.log(0.3 / 0.7), 0.1])
+def test_oracle_at_non_zero_iso_levels_matches_the_numpy_restatement(iso):
+    """everything above pins the oracle at iso 0 only; tests/test_gpu_mcubes.py leans on it at other levels.  On a
+    random grid without on-level values it must give the triangle soup of the independent restatement (mc_ref)."""
+    rng = np.random.default_rng(5)
+    g = iso + rng.standard_normal((6, 6, 6))
+    assert (g != iso).all()
+    v, t = oracle.marching_cubes(np.pad(g, 1, constant_values=-1e6), iso)
+    ref = mc_ref.marching_cubes_soup(g, iso)
+    assert len(t) == len(ref) > 100
+    assert mc_ref.canon(v[t]) == mc_ref.canon(ref)
+    mc_ref.assert_closed_oriented_manifold(t)
+    # and the level matters: the mesh at iso is not the mesh at 0
+    v0, t0 = oracle.marching_cubes(np.pad(g, 1, constant_values=-1e6), 0.0)
+    assert len(t0) != len(t) or not np.array_equal(t0, t)
