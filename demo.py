@@ -6,6 +6,7 @@ write the reference's output files.
   python demo.py --demo_path demo/inputs/scene0549_00.off --out out/scene0549_00
   python demo.py --synthetic 10 --out out/synth --upsampling_steps 1
   python demo.py --synthetic 10 --out out/synth --with_normals     (PLYs with per-vertex nx ny nz)
+  python demo.py --synthetic 10 --out out/synth --refinement_step 30   (meshes refined against the occupancy field)
 
 Weights: --weight <pretrained_weight.pth> (reference checkpoint, key names kept);
 without it seeded random weights are used (no pretrained weights ship with the
@@ -45,6 +46,9 @@ def build_parser():
     ap.add_argument("--with_normals", action="store_true",
                     help="vertex normals from the occupancy field's gradient (generation.with_normals, "
                          "Generator3D.estimate_normals), written to the mesh PLYs as nx ny nz")
+    ap.add_argument("--refinement_step", type=int, default=None,
+                    help="RMSprop steps of Generator3D.refine_mesh on every mesh (generation.refinement_step; the "
+                         "reference's configs use 0 or 30)")
     return ap
 
 
@@ -55,8 +59,8 @@ def main():
     from rfdnet_amd.iscnet.config import Config
     from rfdnet_amd.iscnet.network import ISCNet
 
-    gen = {k: v for k, v in (('resolution_0', args.resolution_0), ('upsampling_steps', args.upsampling_steps))
-           if v is not None}
+    gen = {k: v for k, v in (('resolution_0', args.resolution_0), ('upsampling_steps', args.upsampling_steps),
+                             ('refinement_step', args.refinement_step)) if v is not None}
     if args.with_normals:
         gen['with_normals'] = True
     if args.config:

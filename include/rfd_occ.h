@@ -262,6 +262,45 @@ int rfd_occ_normals_w8(int n_groups, const double *verts, const int *vend, const
                        const float *table, const float *fc_out_w, float *normals, float *grad, int mode,
                        void *stream);
 
+/* ---- batched mesh refinement (csrc/mesh_refine.hip) ---------------------------------------------------------------------
+ * Generator3D.refine_mesh (generator.py:226-289): RMSprop on the vertices of a mesh against
+ *   mean_f (sigmoid(l(q_f)) - tau)^2 + 0.01 mean_f |nf_f - nt_f|^2,  q_f = e_f0 v0 + e_f1 v1 + e_f2 v2 (e_f: Dirichlet weights),
+ * nf = the face normal c / (|c| + 1e-10), nt = -s' g / (s' |g| + 1e-10) with l, g = the decoder's logit and input gradient at
+ * q_f, s = sigmoid(l).  The decoder is piecewise linear in q, so the reference's double backward reduces to l, g and the
+ * sigmoid's derivatives.  One step, all K meshes of a scene together:
+ *   rfd_refine_sample -> rfd_occ_decode_w8 (logits) + rfd_occ_normals_w8 (grad) -> rfd_refine_face_backward ->
+ *   rfd_refine_vertex_step
+ *  F, K       faces of all meshes, number of meshes
+ *  verts      [V][3] f32 vertices of all meshes back to back (updated in place by the vertex step)
+ *  faces      [F][3] int32, vertex indices LOCAL to the face's mesh; a face with an index outside its mesh is inert
+ *             (samples the origin, contributes zero gradient)
+ *  fend, vend [K+1] int32 face / vertex offsets of the meshes (fend[0] = vend[0] = 0, fend[K] = F)
+ *  tprefix    [K+1] int32 decoder-tile offsets: mesh k owns the query slots 128 tprefix[k] .. 128 tprefix[k+1] - 1, its
+ *             face j at slot 128 tprefix[k] + j (tprefix[k+1] - tprefix[k] >= ceil(faces of k / 128))
+ *  eps        [F][3] f32 barycentric weights of this step
+ *  qd         [F][3] f64 out: the sample points, compact -- rfd_occ_normals_w8's `verts` with fend as its `vend`
+ *  qt         [128 tprefix[K]][3] f32 out: the same points at their slots -- rfd_occ_decode_w8's `pts`; padding slots are
+ *             not written (the caller zeroes the buffer once)
+ *  logits     rfd_occ_decode_w8's output for qt;  grad [F][3] f32: rfd_occ_normals_w8's `grad` for qd
+ *  tau        Generator3D.threshold (a probability)
+ *  cg         [F][3][3] f64 out: d loss / d (corner c of face f), loss = the face's mesh's own mean.  Every term is fp32;
+ *             their sum is carried in f64 here and over a vertex's corners (a zero-area face (i, i, j) has a normal term
+ *             ~1e10 times the rest that cancels exactly between its two corners at i -- in fp32 the rest would be absorbed first)
+ * rfd_refine_vertex_step: G[v] = sum of cg[col[i]] for i = rowptr[v] .. rowptr[v+1]-1 in that order (rowptr [V+1], col: corner
+ * ids 3 f + c < n_corners -- the vertex -> corner CSR, built once per call; no atomics), then torch.optim.RMSprop([v],
+ * lr=1e-4)'s defaults: sq = 0.99 sq + 0.01 G^2, v -= 1e-4 G / (sqrt(sq) + 1e-8); sq [V][3] zero before the first step; gout
+ * [V][3] f32 (or NULL) receives G, rounded to fp32 once.  A vertex without corners keeps its bits.
+ * rfd_refine_dirichlet: out [n][3] = Dirichlet(1/2, 1/2, 1/2) rows, z_i^2 / sum_j z_j^2 of three normals from a counter-based
+ * hash of (seed, step, row): the distribution of np.random.dirichlet((.5, .5, .5)), not its stream. */
+int rfd_refine_sample(int F, int K, const float *verts, const int *faces, const int *fend, const int *vend,
+                      const int *tprefix, const float *eps, double *qd, float *qt, void *stream);
+int rfd_refine_face_backward(int F, int K, const float *verts, const int *faces, const int *fend, const int *vend,
+                             const int *tprefix, const float *eps, const float *logits, const float *grad, float tau,
+                             double *cg, void *stream);
+int rfd_refine_vertex_step(int V, const int *rowptr, const int *col, int n_corners, const double *cg, float *verts,
+                           float *sq, float *gout, void *stream);
+int rfd_refine_dirichlet(int n, unsigned long long seed, int step, float *out, void *stream);
+
 /* ---- fp32-class GEMM on the f16 matrix cores (csrc/gemm_f16x3.hip) -----------------
  * C[M,N] = act(A)[M,K] . W[N,K]^T (+ bias[N]) (+ gbias[m / rows_per_group][N]) (+ R[M,N]),
  * optional ReLU on A and on C; three f16 MFMAs per product on (hi, lo) operand splits.

@@ -45,6 +45,10 @@ ABI = {
     "rfd_occ_set_launch_shape": (_i, [_i, _i, _i]),
     "rfd_occ_set_tail_tiles": (_i, [_i]),
     "rfd_occ_normals_w8": (_i, [_i, _f, _f, _f, _i, _f, _f, C.POINTER(C.c_int), _f, _f, _f, _f, _f, _i, _f]),
+    "rfd_refine_sample": (_i, [_i, _i, _f, _f, _f, _f, _f, _f, _f, _f, _f]),
+    "rfd_refine_face_backward": (_i, [_i, _i, _f, _f, _f, _f, _f, _f, _f, _f, _fl, _f, _f]),
+    "rfd_refine_vertex_step": (_i, [_i, _f, _f, _i, _f, _f, _f, _f, _f]),
+    "rfd_refine_dirichlet": (_i, [_i, C.c_ulonglong, _i, _f, _f]),
     "rfd_fps_set_timeout_ms": (_i, [_i]),
     "rfd_fps_set_geometry": (_i, [_i]),
     "rfd_test_hold_cus": (_i, [_i, _f, _i, _f], OPTIONAL),

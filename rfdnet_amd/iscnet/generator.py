@@ -8,7 +8,9 @@ The reference walks the proposals one by one (generator.py:71-74), decodes
 CPU octree per proposal (:99-117).  Here ALL proposals advance together: one
 fused decode launch per MISE round over the concatenated query lists, the MISE
 state (values / point flags / octree flags) is dense and device-resident
-(csrc/mise.hip), and only K 4-byte counters per round cross PCIe.
+(csrc/mise.hip), and only K 4-byte counters per round cross PCIe.  The optional mesh
+refinement (generator.py:226-289, one autograd loop per mesh in the reference) is
+one device loop over all K meshes as well: set_refinement() / refine_meshes().
 """
 import os
 
@@ -16,7 +18,7 @@ import numpy as np
 import torch
 
 from .. import _lib
-from .occ_decoder import TILE, run_with_range_fallback
+from .occ_decoder import MODE_F16X3, TILE, run_with_range_fallback
 
 
 class Mesh(object):
@@ -29,14 +31,44 @@ class Mesh(object):
         self.vertex_normals = vertex_normals
 
 
+def draw_dirichlet(face_counts, steps):
+    """The barycentric weights of `steps` refinement steps for meshes of face_counts faces -> (steps, sum, 3) f32, drawn from
+    numpy's global stream mesh by mesh, step by step: the order of the reference's per-object loop (generator.py:71-74 around
+    :254-260), so a seeded run consumes the same stream.  Rounded to f32 as the reference uploads them (:260)."""
+    total = int(sum(face_counts))
+    out = np.empty((steps, total, 3), dtype=np.float32)
+    at = 0
+    for n in face_counts:
+        for it in range(steps):
+            if n:                   # the reference never refines an empty mesh (generator.py:186-187)
+                out[it, at:at + n] = np.random.dirichlet((0.5, 0.5, 0.5), size=n)
+        at += n
+    return out
+
+
+def vertex_corner_csr(faces, n_vertices):
+    """faces (F,3) integer tensor of GLOBAL vertex indices -> (rowptr (n_vertices + 1,) i32, col (3F,) i32): the corners
+    3 f + c of vertex v are col[rowptr[v]:rowptr[v+1]], ascending (a stable sort of the flattened faces).  A vertex no face
+    names has an empty row; an index outside [0, n_vertices) is in no row."""
+    flat = faces.reshape(-1).long()
+    assert flat.numel() < 2 ** 31
+    flat = torch.where((flat >= 0) & (flat < n_vertices), flat, torch.full_like(flat, n_vertices))
+    col = torch.sort(flat, stable=True).indices
+    rowptr = torch.zeros(n_vertices + 1, dtype=torch.int64, device=faces.device)
+    rowptr[1:] = torch.cumsum(torch.bincount(flat, minlength=n_vertices + 1)[:n_vertices], 0)
+    return rowptr.int(), col.int()
+
+
 class Generator3D(object):
     def __init__(self, model, points_batch_size=100000, threshold=0.5, refinement_step=0,
                  resolution0=16, upsampling_steps=3, with_normals=False, padding=0.1,
                  sample=False, use_cls_for_completion=False, simplify_nfaces=None,
                  preprocessor=None):
         if refinement_step or simplify_nfaces is not None:
-            # disabled by ISCNet_test.yaml:64-66; refine_mesh / libsimplify are out of scope
-            raise NotImplementedError("refinement / simplification are not on the hot path")
+            # disabled by ISCNet_test.yaml:64-66; libsimplify is out of scope (SURVEY.md §2.1 #9), refinement is switched on
+            # by set_refinement() (ONet does, from generation.refinement_step)
+            raise NotImplementedError("simplification is not implemented; refinement is enabled with "
+                                      "Generator3D.set_refinement(steps), not by the constructor")
         self.model = model
         self.round_hook = None
         self.points_batch_size = points_batch_size      # kept for signature parity; no chunking needed
@@ -55,7 +87,27 @@ class Generator3D(object):
         self.sparse_round_points = int(os.environ.get('RFD_MISE_SPARSE_POINTS', 1024))     # (the variable: A/B runs only)
         self.stats = {}
         self.last_normals = None        # with_normals: the (V,3) f32 normals of the last extract_meshes(), all meshes
+        self.refine_eps_source, self.refine_seed = 'numpy', None       # set_refinement()
         self._round0_cache = _lib.ArtefactCache(64)     # made here: the worker views of one network share it
+
+    def set_refinement(self, steps, eps_source='numpy', seed=None):
+        """Refine every extracted mesh by `steps` RMSprop steps (the reference's refinement_step; 0 = off).  eps_source: where
+        the steps' barycentric weights come from -- 'numpy' (np.random.dirichlet from the global stream in the reference's
+        order, draw_dirichlet()) or 'device' (drawn by the GPU from `seed`: same distribution, another stream; for scenes
+        whose host draw would be too large.  seed=None: taken from numpy's global stream at every call).
+        'numpy' reproduces a seeded reference run with ONE scene in flight: numpy's global stream is shared by every host
+        thread, so scenes refined concurrently interleave their draws.  A stage that is run again by the f16-range fallback
+        starts from the stream's state at its first run (ISCNet.complete, refine_mesh): the stream is consumed once."""
+        steps = int(steps)
+        if steps < 0:
+            raise ValueError("refinement steps must be >= 0")
+        if eps_source not in ('numpy', 'device'):
+            raise ValueError("eps_source must be 'numpy' or 'device'")
+        self.refinement_step, self.refine_eps_source, self.refine_seed = steps, eps_source, seed
+        return self
+
+    def _needs_fold(self):
+        return self.with_normals or self.refinement_step > 0
 
     # ---- reference-shaped entry points ------------------------------------------
     def generate_mesh(self, object_features, cls_codes, return_stats=True):
@@ -63,12 +115,12 @@ class Generator3D(object):
         vertex_normals (generator.py:173-176), all K meshes in one launch after marching cubes."""
         fold = []
         grids = self.generate_grids(object_features, cls_codes, fold_out=fold)
-        return self.extract_meshes(grids, fold=fold[0] if self.with_normals else None)
+        return self.extract_meshes(grids, fold=fold[0] if self._needs_fold() else None)
 
     def generate_from_latent(self, z, c=None, device='cuda', **kwargs):
         fold = []
         grids = self._grids(z, c, fold_out=fold)
-        return self.extract_meshes(grids, fold=fold[0] if self.with_normals else None)[0]
+        return self.extract_meshes(grids, fold=fold[0] if self._needs_fold() else None)[0]
 
     def eval_points(self, p, z, c=None, device='cuda', **kwargs):
         """p (T,3) -> logits (T,) for one code (generator.py:123-143)."""
@@ -210,7 +262,8 @@ class Generator3D(object):
     # ---- mesh extraction ------------------------------------------------------------
     def extract_meshes(self, grids, fold=None):
         """fold = (table, fc_p_w) of the codes the grids came from: vertex normals from the decoder's gradient
-        (Generator3D.estimate_normals), one launch for all meshes"""
+        (Generator3D.estimate_normals), one launch for all meshes; with set_refinement(), the refinement of all meshes
+        (refine_meshes) -- after the normals, which belong to the unrefined vertices as in the reference (generator.py:173-195)"""
         from .mcubes import marching_cubes_batch
         thr = self.logit_threshold()
         n = grids.shape[1]
@@ -224,14 +277,113 @@ class Generator3D(object):
         a = box_size / (n - 1)
         v, f, vend, tend = marching_cubes_batch(grids, thr, pad_value=-1e6, return_flat=True,
                                                 affine=(a, -1.5 * a - 0.5 * box_size))
-        self.last_buffers = (v, f, vend, tend)
         self.last_normals = None
-        if fold is None:
-            return [Mesh(v[vend[k]:vend[k + 1]], f[tend[k]:tend[k + 1]]) for k in range(len(vend) - 1)]
-        # generator.py:173-176: normals of every non-empty mesh; the reference leaves them None on an empty one
-        nrm = self.last_normals = self.model.decoder.normals(v, vend, fold[0], fold[1])
+        refine = self.refinement_step > 0
+        if refine and fold is None:
+            raise ValueError("refinement needs fold = (table, fc_p_w) of the meshes' codes (DecoderCBatchNorm.fold)")
+        nrm = None
+        if fold is not None and (self.with_normals or not refine):
+            # generator.py:173-176: normals of every non-empty mesh; the reference leaves them None on an empty one
+            nrm = self.last_normals = self.model.decoder.normals(v, vend, fold[0], fold[1])
+        if refine:
+            v = self.refine_meshes(v, f, vend, tend, fold, self.refinement_step)
+        self.last_buffers = (v, f, vend, tend)
         return [Mesh(v[vend[k]:vend[k + 1]], f[tend[k]:tend[k + 1]],
-                     nrm[vend[k]:vend[k + 1]] if vend[k + 1] > vend[k] else None) for k in range(len(vend) - 1)]
+                     nrm[vend[k]:vend[k + 1]] if nrm is not None and vend[k + 1] > vend[k] else None)
+                for k in range(len(vend) - 1)]
+
+    # ---- refinement (generator.py:226-289) -----------------------------------------------
+    def device_weights(self, n, seed, step, device):
+        """(n,3) f32 Dirichlet(1/2,1/2,1/2) rows of refinement step `step` drawn on `device` (eps_source='device')"""
+        out = torch.empty(n, 3, dtype=torch.float32, device=device)
+        _lib.call("rfd_refine_dirichlet", device, n, int(seed) & (2 ** 64 - 1), int(step), out.data_ptr())
+        return out
+
+    @torch.no_grad()
+    def refine_meshes(self, v, f, vend, tend, fold, steps, eps=None, return_grad=False):
+        """Generator3D.refine_mesh for ALL meshes of the flat marching-cubes buffers in one device loop (csrc/mesh_refine.hip):
+        v (V,3) f64 / f32 vertices, f (F,3) i32 faces with indices local to their mesh, vend / tend the K + 1 vertex / face
+        offsets, fold = (table, fc_p_w) of the K codes.  -> refined vertices (V,3) f32 (a new tensor: v is the kept v0)
+        [, the first step's vertex gradient (V,3) f32].  eps: the weights, (steps, F, 3), instead of a draw (set_refinement's
+        eps_source).  Every mesh has its own loss (its own means) and its own RMSprop state, as in the reference's per-object
+        loop; empty meshes take no part.  Asynchronous, no host round trip inside the loop: the f16-range flag (status bit 2)
+        is left in the stream's status word for the caller's run_with_range_fallback, which starts again from v0."""
+        dec = self.model.decoder
+        if dec.mode != MODE_F16X3:
+            raise NotImplementedError("mesh refinement needs the parity mode (MODE_F16X3); MODE_F16X1 is not supported")
+        if dec.kernel != "w8":
+            raise NotImplementedError("mesh refinement uses the eight-wave decoder's weight stream (kernel 'w8')")
+        vend, tend = [int(x) for x in vend], [int(x) for x in tend]
+        K, V, F = len(vend) - 1, vend[-1], tend[-1]
+        assert len(tend) == K + 1 and vend[0] == 0 and tend[0] == 0 and v.is_cuda and v.shape[0] >= V and f.shape[0] >= F
+        dev = v.device
+        vr = v[:V].to(torch.float32, copy=True).contiguous()                     # generator.py:245-246
+        grad0 = torch.zeros(V, 3, dtype=torch.float32, device=dev) if return_grad else None
+        if steps > 0 and F > 0:
+            table, fc_p_w = fold
+            assert table.shape[0] >= K
+            counts = [tend[k + 1] - tend[k] for k in range(K)]
+            tiles = [(n + TILE - 1) // TILE for n in counts]
+            tprefix = np.concatenate([[0], np.cumsum(tiles)])
+            gprefix = np.concatenate([[0], np.cumsum([(n + 15) // 16 for n in counts])])
+            bounds = torch.from_numpy(np.stack([tend, vend, tprefix, gprefix]).astype(np.int32)).to(dev)
+            fend_d, vend_d, tprefix_d, gprefix_d = bounds[0], bounds[1], bounds[2], bounds[3]
+            tile_prop = torch.from_numpy(np.repeat(np.arange(K, dtype=np.int32), tiles)).to(dev)
+            faces = f[:F].to(torch.int32).contiguous()
+            first = torch.repeat_interleave(vend_d[:-1].long(), torch.as_tensor(counts, device=dev), output_size=F)
+            rowptr, col = vertex_corner_csr(faces.long() + first[:, None], V)
+            if eps is not None:
+                eps = torch.as_tensor(np.ascontiguousarray(eps, dtype=np.float32)) if not torch.is_tensor(eps) else eps
+                assert tuple(eps.shape) == (steps, F, 3)
+                eps = eps.to(dev, torch.float32).contiguous()
+            elif self.refine_eps_source == 'numpy':
+                eps = torch.from_numpy(draw_dirichlet(counts, steps)).to(dev)
+            else:
+                seed = self.refine_seed if self.refine_seed is not None else int(np.random.randint(0, 2 ** 31 - 1))
+            qd = torch.empty(F, 3, dtype=torch.float64, device=dev)
+            qt = torch.zeros(int(tprefix[-1]) * TILE, 3, dtype=torch.float32, device=dev)     # padding slots stay zero
+            cg = torch.empty(F, 3, 3, dtype=torch.float64, device=dev)     # f64: csrc/mesh_refine.hip's header says why
+            sq = torch.zeros(V, 3, dtype=torch.float32, device=dev)
+            g = torch.empty(F, 3, dtype=torch.float32, device=dev)
+            nrm = torch.empty(F, 3, dtype=torch.float32, device=dev)                          # the normals kernel's other output
+            input_grad = dec.input_grad_launcher(table, fc_p_w, K, int(gprefix[-1]), fend_d, gprefix_d)
+            tau = float(self.threshold)
+            for it in range(steps):
+                e = eps[it] if eps is not None else self.device_weights(F, seed, it, dev)
+                _lib.call("rfd_refine_sample", dev, F, K, vr.data_ptr(), faces.data_ptr(), fend_d.data_ptr(),
+                          vend_d.data_ptr(), tprefix_d.data_ptr(), e.data_ptr(), qd.data_ptr(), qt.data_ptr())
+                logits = dec.decode_tiles(qt, tile_prop, table, fc_p_w)
+                input_grad(qd, nrm, g)
+                _lib.call("rfd_refine_face_backward", dev, F, K, vr.data_ptr(), faces.data_ptr(), fend_d.data_ptr(),
+                          vend_d.data_ptr(), tprefix_d.data_ptr(), e.data_ptr(), logits.data_ptr(), g.data_ptr(), tau,
+                          cg.data_ptr())
+                _lib.call("rfd_refine_vertex_step", dev, V, rowptr.data_ptr(), col.data_ptr(), 3 * F, cg.data_ptr(),
+                          vr.data_ptr(), sq.data_ptr(), grad0.data_ptr() if return_grad and it == 0 else None)
+        return (vr, grad0) if return_grad else vr
+
+    def refine_mesh(self, mesh, occ_hat, z, c=None, device='cuda'):
+        """generator.py:226-289: moves mesh.vertices (numpy or tensor (V,3); mesh.faces (F,3)) by self.refinement_step steps
+        for one code z (Z,), c (C,); occ_hat is not used (the reference only reads its shape).  -> mesh"""
+        dec = self.model.decoder
+        if c is None:
+            raise ValueError("refinement needs the code c (the decoder is conditioned on it)")
+        dev = c.device if c.is_cuda else torch.device(device)
+        as_numpy = not torch.is_tensor(mesh.vertices)
+        v = torch.as_tensor(np.ascontiguousarray(mesh.vertices) if as_numpy else mesh.vertices).to(dev)
+        f = torch.as_tensor(np.ascontiguousarray(mesh.faces) if not torch.is_tensor(mesh.faces) else mesh.faces)
+        f = f.to(dev, torch.int32).reshape(-1, 3)
+        if v.shape[0] == 0 or not self.refinement_step:
+            return mesh
+        with torch.no_grad():
+            z, c = z.reshape(1, -1).float().to(dev), c.reshape(1, -1).float().to(dev)
+            # the numpy stream must not be drawn from twice when the range fallback runs the loop again
+            eps = None
+            if self.refine_eps_source == 'numpy':
+                eps = draw_dirichlet([f.shape[0]], self.refinement_step)
+            out = run_with_range_fallback(dec, lambda: self.refine_meshes(
+                v, f, [0, v.shape[0]], [0, f.shape[0]], dec.fold(z, c), self.refinement_step, eps=eps), dev)
+        mesh.vertices = out.cpu().numpy() if as_numpy else out
+        return mesh
 
     def estimate_normals(self, vertices, z, c=None, device='cuda'):
         """generator.py:200-224: vertices (V,3) numpy (rounded to fp32 like torch.FloatTensor), one code z (Z,), c (C,)
@@ -248,4 +400,10 @@ class Generator3D(object):
         g = torch.as_tensor(occ_hat, dtype=torch.float32)
         if not g.is_cuda:
             g = g.cuda()
-        return self.extract_meshes(g.unsqueeze(0))[0]
+        fold = None
+        if self.refinement_step > 0:                                 # generator.py:194-195
+            if c is None:
+                raise ValueError("refinement needs the code c (the decoder is conditioned on it)")
+            with torch.no_grad():
+                fold = self.model.decoder.fold(z.reshape(1, -1).float().to(g.device), c.reshape(1, -1).float().to(g.device))
+        return self.extract_meshes(g.unsqueeze(0), fold=fold)[0]

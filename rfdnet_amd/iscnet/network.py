@@ -241,7 +241,15 @@ class ISCNet(nn.Module):
         def stage_flags():
             if before.read():
                 raise _StageFlag(before.read())
-        return run_with_range_fallback(self.completion.decoder, lambda: run(codes, cls), device,
+        # refinement draws its weights from numpy's global stream: a second run (the range fallback) starts from the
+        # state the first one started from, so the stream is consumed once, as by the reference
+        rng = np.random.get_state() if getattr(gen, 'refinement_step', 0) > 0 and gen.refine_eps_source == 'numpy' else None
+
+        def stage():
+            if rng is not None:
+                np.random.set_state(rng)
+            return run(codes, cls)
+        return run_with_range_fallback(self.completion.decoder, stage, device,
                                        None if before is None else stage_flags)
 
     @staticmethod

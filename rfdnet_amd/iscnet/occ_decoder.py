@@ -173,15 +173,27 @@ class DecoderCBatchNorm(nn.Module):
         normals = torch.empty(V, 3, dtype=torch.float32, device=dev)
         grad = torch.empty(V, 3, dtype=torch.float32, device=dev) if return_grad else None
         if gprefix[-1]:
-            packed, kw0, kw1 = self.packed_weights()
-            packed_b, kb0, kb1 = self.packed_weights_bwd()
             bounds = torch.tensor([vend, gprefix], dtype=torch.int32).to(dev, non_blocking=True)
-            wo = self.fc_out.weight.detach().reshape(-1).contiguous()
-            kw = (C.c_int * 12)(*(list(kw0) + [kw1] + list(kb0) + [kb1]))
-            _lib.call("rfd_occ_normals_w8", dev, gprefix[-1], verts.data_ptr(), bounds[0].data_ptr(),
-                      bounds[1].data_ptr(), K, packed.data_ptr(), packed_b.data_ptr(), kw, fc_p_w.data_ptr(),
-                      table.data_ptr(), wo.data_ptr(), normals.data_ptr(), _lib.ptr(grad), self.mode)
+            self.input_grad_launcher(table, fc_p_w, K, gprefix[-1], bounds[0], bounds[1])(verts, normals, grad)
         return (normals, grad) if return_grad else normals
+
+    def input_grad_launcher(self, table, fc_p_w, K, n_groups, vend, gprefix):
+        """-> launch(verts (V,3) f64, normals (V,3) f32 out, grad (V,3) f32 out or None): rfd_occ_normals_w8 for K meshes
+        whose vertex / 16-group offsets are the DEVICE int32 tensors vend / gprefix (K + 1 each, n_groups = the last group
+        offset).  For callers that launch many times on the same offsets (the refinement loop): nothing is uploaded per
+        launch."""
+        packed, kw0, kw1 = self.packed_weights()
+        packed_b, kb0, kb1 = self.packed_weights_bwd()
+        wo = self.fc_out.weight.detach().reshape(-1).contiguous()
+        kw = (C.c_int * 12)(*(list(kw0) + [kw1] + list(kb0) + [kb1]))
+        assert vend.dtype == torch.int32 and gprefix.dtype == torch.int32 and vend.is_cuda and gprefix.is_cuda
+
+        def launch(verts, normals, grad):
+            assert verts.dtype == torch.float64 and verts.is_contiguous() and normals.dtype == torch.float32
+            _lib.call("rfd_occ_normals_w8", verts.device, n_groups, verts.data_ptr(), vend.data_ptr(), gprefix.data_ptr(),
+                      K, packed.data_ptr(), packed_b.data_ptr(), kw, fc_p_w.data_ptr(), table.data_ptr(), wo.data_ptr(),
+                      normals.data_ptr(), _lib.ptr(grad), self.mode)
+        return launch
 
     def input_grad(self, p, z, c):
         """d logit / d p of forward(p, z, c) (p (B,T,3)) -> (B,T,3) f32, with the f16-range flag answered like forward()'s."""

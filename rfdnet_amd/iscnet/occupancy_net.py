@@ -31,9 +31,11 @@ class ONet(nn.Module):
             self.generator = Generator3D(
                 self, threshold=data['threshold'], resolution0=gen['resolution_0'],
                 upsampling_steps=gen['upsampling_steps'], sample=gen['use_sampling'],
-                refinement_step=gen['refinement_step'], simplify_nfaces=gen['simplify_nfaces'],
+                refinement_step=0, simplify_nfaces=gen['simplify_nfaces'],
                 with_normals=gen.get('with_normals', False),
                 preprocessor=None)
+            if gen['refinement_step']:
+                self.generator.set_refinement(gen['refinement_step'])
 
     def get_prior_z(self, z_dim, device):
         return dist.Normal(torch.zeros(z_dim, device=device), torch.ones(z_dim, device=device))
