@@ -255,7 +255,7 @@ int rfd_occ_chunk_range_capped(int k, int n_tiles, int n_workgroups, int max_chu
  *             ni / torch.norm(ni) gives)
  *  grad       [V][3] f32 out (or NULL): g itself
  *  mode       RFD_OCC_MODE_F16X3 only (anything else: hipErrorInvalidValue)
- * Status bit 2 (the stream's status word): an activation of the forward pass, or a back-propagated value, beyond the f16
+ * RFD_STATUS_DECODER_RANGE (the stream's status word, rfd_pointnet2.h): an activation of the forward pass, or a back-propagated value, beyond the f16
  * range at the table's scale -- the same flag and the same answer (refold at the fallback scale) as the decoder. */
 int rfd_occ_normals_w8(int n_groups, const double *verts, const int *vend, const int *gprefix, int K,
                        const void *packed_fwd, const void *packed_bwd, const int *kw, const float *fc_p_w,
@@ -361,7 +361,7 @@ int rfd_gemm_f16x3_frag(int M, int N, int K, const void *A_frag, long a_rb_strid
  * x [M][ldx] (first d <= 8 columns), mask [M], W [N][ldw] (first d columns), bias [N],
  * group [M / rows_per_group][N] = box_feature . W[:, d:]^T, out [M][ldo] (may be a column
  * window of a wider row-major buffer).  N % 4 == 0, ldo % 4 == 0.  sa = the activation scale exponent of
- * the split-precision GEMM that consumes `out` (status bit 4 when |out| 2^sa would leave the f16 range). */
+ * the split-precision GEMM that consumes `out` (RFD_STATUS_GEMM_RANGE when |out| 2^sa would leave the f16 range). */
 int rfd_pos_embed(int M, int N, int d, const float *x, int ldx, const float *mask,
                   const float *W, int ldw, const float *bias, const float *group,
                   int rows_per_group, float *out, int ldo, int sa, void *stream);
@@ -381,7 +381,7 @@ int rfd_pos_embed_frag(int M, int N, int d, const float *x, int ldx, const float
  * group's points).
  * rfd_chain_pack_n splits the weights (scaled by 2^sw, |w| 2^sw <= 2^14) into f16 (hi, lo) MFMA fragments:
  * rfd_chain_packed_bytes_n(c3) bytes.  rfd_chain_pool_n: x [M][ldx] fp32 rows, P % 512 == 0, M % P == 0,
- * out [M / P][c3].  sa = activation scale exponent (status bit 4 when |activation| 2^sa leaves the f16 range). */
+ * out [M / P][c3].  sa = activation scale exponent (RFD_STATUS_GEMM_RANGE when |activation| 2^sa leaves the f16 range). */
 size_t rfd_chain_packed_bytes_n(int c3);
 int rfd_chain_pack_n(int mode, int c3, const float *W1, const float *W2, const float *W3, int sw1, int sw2, int sw3,
                      void *packed, void *stream);

@@ -125,11 +125,14 @@ int rfd_furthest_point_sampling_gather(int b, int n, int m,
 
 /* ---- diagnostics --------------------------------------------------------- */
 const char *rfd_last_error_string(void);
-/* Device-side status words of the persistent kernels (bit 0: a multi-workgroup FPS launch
- * ABORTED on its exchange time-out, see rfd_fps_set_timeout_ms; bit 1: occupancy decoder,
- * bit 2: split-precision GEMMs -- an activation beyond the f16 range at the current scale).
+/* Device-side status words of the persistent kernels: an OR of the flags below.
  * One word per stream (64 slots per device; slot 0 is the null stream's and the overflow slot).
  * rfd_device_status synchronises the DEVICE and returns / clears the OR of all words.  0 = OK. */
+enum {
+  RFD_STATUS_FPS_ABORT = 1,     /* a multi-workgroup FPS launch ABORTED on its exchange time-out (rfd_fps_set_timeout_ms) */
+  RFD_STATUS_DECODER_RANGE = 2, /* occupancy decoder: an activation beyond the f16 range at the current scale */
+  RFD_STATUS_GEMM_RANGE = 4     /* split-precision GEMMs, pos_embed, PointSeg chains: the same */
+};
 int rfd_device_status(void);
 /* The word of `stream` only, after waiting for that stream (other streams keep
  * running and keep their own flags); cleared when reported. */
@@ -145,7 +148,7 @@ int rfd_release_stream(void *stream);
  * partitioned GPU, a CU-masked queue, another stream's or process's persistent kernel holding the CUs -- the launch does NOT
  * hang: a workgroup whose polling wave has waited `ms` milliseconds (wall clock; default 500, or RFD_FPS_TIMEOUT_MS at
  * load) for one round's candidates raises the launch's sticky abort word, every workgroup of the launch -- running, or
- * dispatched only later -- leaves at once, status bit 0 is raised on the stream and idxs keeps the caller's
+ * dispatched only later -- leaves at once, RFD_STATUS_FPS_ABORT is raised on the stream and idxs keeps the caller's
  * zero-fill beyond the round reached.  (Measured on MI355X: beside a kernel that holds most CUs the hardware usually
  * places NONE of the grid's workgroups and the launch just waits for the CUs, as any launch would; a partially placed
  * grid -- seen with 8 free CUs on the null stream -- ends through the abort.)  The reference's answer to a launch that cannot run is to fail fast as well

@@ -242,16 +242,22 @@ def current_stream():
     return torch.cuda.current_stream().cuda_stream
 
 
+# flags of the device status word (include/rfd_pointnet2.h)
+STATUS_FPS_ABORT = 1
+STATUS_DECODER_RANGE = 2
+STATUS_GEMM_RANGE = 4
+
+
 def _raise_status(st):
     if st < 0:
         raise RfdHipError("rfd_device_status failed")
     msgs = []
-    if st & 1:
+    if st & STATUS_FPS_ABORT:
         msgs.append("furthest point sampling aborted: its workgroups were not resident together within the "
                     "exchange time-out (partitioned / CU-masked / oversubscribed GPU?)")
-    if st & 2:
+    if st & STATUS_DECODER_RANGE:
         msgs.append("occupancy decoder: activation exceeded the f16 range")
-    if st & 4:
+    if st & STATUS_GEMM_RANGE:
         msgs.append("split-precision GEMM: activation exceeded the f16 range")
     if msgs:
         e = RfdHipError("; ".join(msgs))

@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <atomic>
+#include "../../include/rfd_pointnet2.h"   // the RFD_STATUS_* flags of the device status word
 
 #define RFD_API extern "C" __attribute__((visibility("default")))
 
@@ -59,7 +60,7 @@ struct RfdWorkspace {
   int num_cu;                     // multiprocessor count of the device
   int wall_clock_khz;             // rate of wall_clock64() on the device (100 MHz on gfx950)
   std::atomic<int> fps_timeout_ms;  // multi-workgroup FPS: a workgroup that has polled this long for a round's
-                                    // candidates aborts the launch (status bit 0); rfd_fps_set_timeout_ms
+                                    // candidates aborts the launch (RFD_STATUS_FPS_ABORT); rfd_fps_set_timeout_ms
   std::atomic<int> fps_force_ppt;   // 0 = the launcher's own geometry; else points per thread (rfd_fps_set_geometry)
   std::atomic<int> fps_test_phantom;  // exchange units that never publish (rfd_fps_test_phantom_units; tests only)
 };

@@ -23,41 +23,22 @@
 // Operands are pre-scaled by 2^sa / 2^sw (exact) to keep the lo parts in the
 // normal f16 range; the epilogue multiplies by 2^-(sa+sw).
 #include "common.h"
-#include "split_f16.h"
+#include "frag_rows.h"
 #include <stdlib.h>
 
 namespace {
 
-using namespace split_f16;
+using namespace frag_rows;
 
 constexpr int BM = 128, BN = 128, BK = 32;
 constexpr int A_STAGE_BYTES = (BM / 32) * (BK / 16) * 2 * 1024;  // 4 rowblocks x 2 ksteps x (hi,lo) x 1 KiB = 16 KiB
 constexpr int W_STAGE_BYTES = (BN / 32) * (BK / 16) * 2 * 1024;  // 16 KiB
 constexpr int STAGE_BYTES = A_STAGE_BYTES + W_STAGE_BYTES;
 
-// W[N][K] fp32 -> fragment stream [N/128][K/32][nb 4][ks 2][split 2][lane 64][8] f16
-__global__ void gemm_pack_w_kernel(int N, int K, int sw, const float *__restrict__ W,
-                                   _Float16 *__restrict__ packed) {
-  const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t total = (size_t)N * K * 2;
-  if (e >= total) return;
-  const int j = e & 7;
-  const int lane = (e >> 3) & 63;
-  const int split = (e >> 9) & 1;
-  const int ks = (e >> 10) & 1;
-  const int nb = (e >> 11) & 3;
-  const size_t rest = e >> 13;
-  const int kiter = (int)(rest % (K / BK));
-  const int ntile = (int)(rest / (K / BK));
-  const int n = ntile * BN + nb * 32 + (lane & 31);
-  const int k = kiter * BK + ks * 16 + 8 * (lane >> 5) + j;
-  const float w = ldexpf(W[(size_t)n * K + k], sw);
-  packed[e] = weight_half(w, split);
-}
-
 // running maximum of |hi| words (two f16 per register): an activation that reaches the f16 limit
 // (|a| 2^sa >= 65504: cvt_pkrtz saturates, the product is silently wrong where the reference's
-// fp32 GEMM is not) raises bit 2 of the device status word, as the decoder does (occ_decoder.hip)
+// fp32 GEMM is not) raises RFD_STATUS_GEMM_RANGE in the device status word, as the decoder raises
+// its own flag (occ_decoder.hip)
 __device__ __forceinline__ unsigned amax_u16(unsigned acc, unsigned hiw, bool nonneg) {
   return pk_max_u16(acc, nonneg ? hiw : (hiw & 0x7fff7fffu));
 }
@@ -75,7 +56,7 @@ struct Args {
   float a_scale, out_scale;     // 2^sa, 2^-(sa+sw)
   float *pool;                  // [M/rows_per_group][N] running max(0, C) per group, or null (row-owner kernel)
   int pool_signed;              // pool holds the plain max (caller initialises it to -inf) instead of max(0, C)
-  unsigned *status;             // device status word (bit 2: an activation left the f16 range)
+  unsigned *status;             // device status word (RFD_STATUS_GEMM_RANGE: an activation left the f16 range)
   // fragment-ordered split activations (gemm_rowsf_kernel): first 4-KiB block of a 32-row block, stride between row blocks
   const unsigned char *Af; long af_stride;
   unsigned char *Cf; long cf_stride;      // Cf may be null (pool only)
@@ -85,23 +66,30 @@ struct Args {
   const float *cb1, *cb2; int cb1_stride, cb2_stride;
 };
 
+// Workgroup -> (m tile, n tile): declares and sets `int ntile, mtile`.  The workgroups sharing an A tile (its n tiles)
+// go to ONE XCD (own L2; workgroups are dealt round-robin to the 8 XCDs), at consecutive dispatch slots.  A macro: as an
+// inlined function the same statements reach gemm_rows8_kernel's pinned instruction stream in another order.
+#define XCD_TILE_MAP(MTILES, NTILES)                       \
+  const int ntiles = (NTILES);                             \
+  int ntile, mtile;                                        \
+  {                                                        \
+    const int mtiles = (MTILES);                           \
+    if (mtiles % 8 == 0) {                                 \
+      const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3; \
+      ntile = j % ntiles;                                  \
+      mtile = (j / ntiles) * 8 + xcd;                      \
+    } else {                                               \
+      ntile = blockIdx.x % ntiles;                         \
+      mtile = blockIdx.x / ntiles;                         \
+    }                                                      \
+  }
+
 __global__ __launch_bounds__(256, 2) void gemm_f16x3_kernel(Args g) {
   __shared__ __attribute__((aligned(16))) unsigned char smem[2 * STAGE_BYTES];
   const int t = threadIdx.x, lane = t & 63;
   const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
   const int wm = wave >> 1, wn = wave & 1;        // wave position in the 2 x 2 grid
-  // the workgroups sharing an A tile (its n tiles) go to ONE XCD (own L2; workgroups are
-  // dealt round-robin to the 8 XCDs), at consecutive dispatch slots
-  const int ntiles = g.N / BN;
-  int ntile, mtile;
-  if ((g.M / BM) % 8 == 0) {
-    const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
-    ntile = j % ntiles;
-    mtile = (j / ntiles) * 8 + xcd;
-  } else {
-    ntile = blockIdx.x % ntiles;
-    mtile = blockIdx.x / ntiles;
-  }
+  XCD_TILE_MAP(g.M / BM, g.N / BN);
   const int m0 = mtile * BM, n0 = ntile * BN;
   const int kiters = g.K / BK;
 
@@ -126,16 +114,13 @@ __global__ __launch_bounds__(256, 2) void gemm_f16x3_kernel(Args g) {
       for (int e = 0; e < 4; e += 2) {
         float a0 = r[q][e] * g.a_scale, a1 = r[q][e + 1] * g.a_scale;
         if (g.relu_in) { a0 = a0 > 0.f ? a0 : 0.f; a1 = a1 > 0.f ? a1 : 0.f; }
-        const half2v h2 = __builtin_bit_cast(half2v, __builtin_amdgcn_cvt_pkrtz(a0, a1));
-        const float r0 = a0 - (float)h2[0], r1 = a1 - (float)h2[1];
-        hw[q * 2 + e / 2] = __builtin_bit_cast(unsigned, h2);
+        split2_sub(a0, a1, hw[q * 2 + e / 2], lw[q * 2 + e / 2]);
         amax16 = amax_u16(amax16, hw[q * 2 + e / 2], false);
-        lw[q * 2 + e / 2] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(r0, r1));
       }
     }
     const int l0 = arow & 31;
     u32x4 *hi = reinterpret_cast<u32x4 *>(base);
-    u32x4 *lo = reinterpret_cast<u32x4 *>(base + 1024);
+    u32x4 *lo = reinterpret_cast<u32x4 *>(base + FRAG_RUN_BYTES);
     hi[l0] = u32x4{hw[0], hw[1], hw[2], hw[3]};
     hi[l0 + 32] = u32x4{hw[4], hw[5], hw[6], hw[7]};
     lo[l0] = u32x4{lw[0], lw[1], lw[2], lw[3]};
@@ -197,7 +182,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f16x3_kernel(Args g) {
     __syncthreads();
   }
 
-  flag_f16_range(amax16, g.status, 4u);
+  flag_f16_range(amax16, g.status, RFD_STATUS_GEMM_RANGE);
   // ---- epilogue: scale back, add bias / group bias / residual, ReLU, store
   const int half = lane >> 5, nl = lane & 31;
   float omax = 0.f;
@@ -218,7 +203,9 @@ __global__ __launch_bounds__(256, 2) void gemm_f16x3_kernel(Args g) {
         g.C[(size_t)m * g.ldc + n] = v;
       }
     }
-  if (omax * g.a_scale >= 65504.f) atomicOr(g.status, 4u);    // would overflow the next layer's split
+  // would overflow the next layer's split (the branch is written out here and in rows_epilogue: as part of an inlined
+  // flag_out_range it moves these two kernels' blocks)
+  if (out_of_f16_range(omax, g.a_scale)) atomicOr(g.status, RFD_STATUS_GEMM_RANGE);
 }
 
 
@@ -240,27 +227,6 @@ __global__ __launch_bounds__(256, 2) void gemm_f16x3_kernel(Args g) {
 // Per 32-wide k piece a CU moves 64 KiB (32 KiB x fp32, 32 KiB W) for 12.6 MFLOP issued.
 constexpr int RM = 256, RN = 256, RK = 32;
 constexpr int R_PIECE_BYTES = 32 * 1024;
-
-// layout 2: [N/256][K/32][kstep 2][blk 8][split 2][lane 64][8] f16,
-// n = 256 ntile + 32 blk + (lane & 31), k = 32 piece + 16 (lane >> 5) + 8 kstep + j
-__global__ void gemm_pack_rows_kernel(int N, int K, int sw, const float *__restrict__ W,
-                                      _Float16 *__restrict__ packed) {
-  const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t total = (size_t)N * K * 2;
-  if (e >= total) return;
-  const int j = e & 7;
-  const int lane = (e >> 3) & 63;
-  const int split = (e >> 9) & 1;
-  const int blk = (e >> 10) & 7;
-  const int kstep = (e >> 13) & 1;
-  const size_t rest = e >> 14;
-  const int piece = (int)(rest % (K / RK));
-  const int ntile = (int)(rest / (K / RK));
-  const int n = ntile * RN + blk * 32 + (lane & 31);
-  const int k = piece * RK + 16 * (lane >> 5) + 8 * kstep + j;
-  const float w = ldexpf(W[(size_t)n * K + k], sw);
-  packed[e] = weight_half(w, split);
-}
 
 template <int N>
 __device__ __forceinline__ void wait_vm() {
@@ -289,17 +255,23 @@ __device__ __forceinline__ float dpp_max(float v) {
 // otherwise every wave finishes its own columns.  The atomics cross the XCDs' private L2s and
 // were the limit of these launches (8.4 M per K = 128 layer), not the arithmetic.
 // max commutes with the monotone fma / ReLU, so the result is bit-identical to rows_epilogue's.
+// Running float maximum on integer atomics: non-negative floats order like their bit patterns as signed ints, negative
+// ones in reverse as unsigned ints; each atomic is a no-op against a stored value of the other sign.  !is_signed: the
+// pool holds max(0, .) (zero-initialised; every consumer rectifies the pooled vector), so v <= 0 changes nothing.
+__device__ __forceinline__ void pool_atomic(int *p, float v, int is_signed) {
+  if (v > 0.f) atomicMax(p, __float_as_int(v));
+  else if (is_signed) {
+    if (v == 0.f) atomicMax(p, 0);          // +-0 -> +0
+    else atomicMin(reinterpret_cast<unsigned *>(p), __float_as_uint(v));
+  }
+}
+
 __device__ __forceinline__ void pool_finish(const Args &g, float v, size_t grp, int c) {
   float o = __builtin_fmaf(v, g.out_scale, g.bias[c] + g.gbias[grp * g.gbias_stride + c]);
   if (g.relu_out) o = o > 0.f ? o : 0.f;
   // the pooled value is the next split GEMM's input: same range watch as the stored outputs
-  if (__builtin_fabsf(o) * g.a_scale >= 65504.f) atomicOr(g.status, 4u);
-  int *p = reinterpret_cast<int *>(g.pool + grp * g.N + c);
-  if (o > 0.f) atomicMax(p, __float_as_int(o));
-  else if (g.pool_signed) {
-    if (o == 0.f) atomicMax(p, 0);          // +-0 -> +0
-    else atomicMin(reinterpret_cast<unsigned *>(p), __float_as_uint(o));
-  }
+  flag_out_range(__builtin_fabsf(o), g.a_scale, g.status, RFD_STATUS_GEMM_RANGE);
+  pool_atomic(reinterpret_cast<int *>(g.pool + grp * g.N + c), o, g.pool_signed);
 }
 
 __device__ __forceinline__ void pool_epilogue(const Args &g, unsigned char *smem, const f32x16 (&acc)[8], int wave,
@@ -410,24 +382,15 @@ __device__ __forceinline__ void rows_epilogue(const Args &g, unsigned char *smem
       // on the outputs because this kernel's k loop is pinned instruction by instruction: one more VALU
       // op in it let the scheduler lift a conversion above its vmcnt wait (tools/audit_vmcnt.py).
       // (pool-only launches included: the pooled maximum feeds the next split GEMM as well)
-      if (omax * g.a_scale >= 65504.f) atomicOr(g.status, 4u);
+      if (out_of_f16_range(omax, g.a_scale)) atomicOr(g.status, RFD_STATUS_GEMM_RANGE);
       if (g.pool) {
-        // fused max-pool over the group's rows (every consumer rectifies the pooled vector, so
-        // max(0, .) is what is needed): non-negative floats order like their bit patterns
+        // fused max-pool over the group's rows
         int *pp = reinterpret_cast<int *>(g.pool + (size_t)(m0 / g.rows_per_group) * g.N + n0 + 128 * p + 4 * l);
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           const float other = __shfl_xor(pmax[e], 32);
           const float v = other > pmax[e] ? other : pmax[e];
-          // non-negative floats order like their bit patterns as signed ints, negative ones in
-          // reverse as unsigned ints; each atomic is a no-op against a stored value of the other sign
-          if (rsel == 0) {
-            if (v > 0.f) atomicMax(pp + e, __float_as_int(v));
-            else if (g.pool_signed) {
-              if (v == 0.f) atomicMax(pp + e, 0);          // +-0 -> +0
-              else atomicMin(reinterpret_cast<unsigned *>(pp + e), __float_as_uint(v));
-            }
-          }
+          if (rsel == 0) pool_atomic(pp + e, v, g.pool_signed);
         }
       }
     }
@@ -449,19 +412,7 @@ __global__ __launch_bounds__(512) void gemm_rows8_kernel(Args g) {
   const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
   const unsigned lane16 = (unsigned)lane * 16u;
   const int half = lane >> 5, n = lane & 31;
-  const int ntiles = g.N / RN;
-  int ntile, mtile;
-  {
-    const int mtiles = g.M / RM;
-    if (mtiles % 8 == 0) {
-      const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
-      ntile = j % ntiles;
-      mtile = (j / ntiles) * 8 + xcd;
-    } else {
-      ntile = blockIdx.x % ntiles;
-      mtile = blockIdx.x / ntiles;
-    }
-  }
+  XCD_TILE_MAP(g.M / RM, g.N / RN);
   const int m0 = mtile * RM + wave * 32, n0 = ntile * RN;
   const int np = g.K / RK;
   const char *wp = reinterpret_cast<const char *>(g.Wp) +
@@ -495,10 +446,7 @@ __global__ __launch_bounds__(512) void gemm_rows8_kernel(Args g) {
       a0 = a0 > 0.f ? a0 : 0.f;
       a1 = a1 > 0.f ? a1 : 0.f;
     }
-    const half2v h2 = __builtin_bit_cast(half2v, __builtin_amdgcn_cvt_pkrtz(a0, a1));
-    const float r0 = a0 - (float)h2[0], r1 = a1 - (float)h2[1];
-    nh[i] = __builtin_bit_cast(unsigned, h2);
-    nl[i] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(r0, r1));
+    split2_sub(a0, a1, nh[i], nl[i]);
   };
   auto conv_finish = [&]() {
     bh = __builtin_bit_cast(half8, u32x4{nh[0], nh[1], nh[2], nh[3]});
@@ -595,56 +543,52 @@ __global__ __launch_bounds__(512) void gemm_rows8_kernel(Args g) {
 // scales and splits the same activations again on the VALU.  Every consumer of an encoder
 // activation rectifies it (layers.py:27,38-46: the in-place ReLU), so the PRODUCER can store
 // relu(x) 2^sa already split into f16 (hi, lo) -- the same 4 bytes per element -- and store it in
-// the order the consumer's matrix instruction wants its B operand:
-//
-//   block (rb, kb) = rows 32 rb .. +31, channels 32 kb .. +31 = 4 KiB:
-//     [kstep 2][split hi / lo][lane 64][8 f16]
-//     row     = 32 rb + (lane & 31)
-//     channel = 32 kb + (r & 3) + 8 (r >> 2) + 4 (lane >> 5),   r = 8 kstep + j
-//
-// i.e. the channel order inside a block is the ACCUMULATOR order of v_mfma_f32_32x32x16 (a lane
+// the order the consumer's matrix instruction wants its B operand (frag_rows.h has the layout and its helpers).
+// The channel order inside a 32 x 32 block is the ACCUMULATOR order of v_mfma_f32_32x32x16 (a lane
 // holds 16 channels of one row), so a producer's epilogue converts its accumulators in registers
 // and writes four fully coalesced 1-KiB runs per block -- no transpose through LDS -- and the
 // consumer's k loop issues four coalesced 16-byte loads per lane and 32-wide k piece whose results
 // ARE the B fragments: no LDS, no VALU, no partial cache lines.  W is packed in the matching k
 // order (layout 3 of rfd_gemm_pack_w).  A buffer is [M / 32][row-block stride]; a column window
 // is a block offset, so [hidden | input] concatenations stay free.
-constexpr int FRAG_BLOCK_BYTES = 4096;
 
-__device__ __host__ __forceinline__ int frag_channel(int kstep, int half, int j) {
-  const int r = 8 * kstep + j;
-  return (r & 3) + 8 * (r >> 2) + 4 * half;
-}
+// W [N][K] fp32 -> one of the three operand streams of rfd_gemm_pack_w: f16 (hi, lo) halves of W 2^sw, element
+// e = [..][split 2][lane 64][j 8] of the stream <- W[n][k]:
+//   PACK_TILE (gemm_f16x3_kernel)   [N/128][K/32][nb 4][kstep 2][split][lane][j]
+//                                   n = 128 ntile + 32 nb + (lane & 31),  k = 32 piece + 16 kstep + 8 (lane >> 5) + j
+//   PACK_ROWS (gemm_rows8_kernel)   [N/256][K/32][kstep 2][blk 8][split][lane][j]
+//                                   n = 256 ntile + 32 blk + (lane & 31), k = 32 piece + 16 (lane >> 5) + 8 kstep + j
+//   PACK_FRAG (gemm_rowsf_kernel)   as PACK_ROWS,                         k = 32 piece + frag_channel(kstep, lane >> 5, j)
+constexpr int PACK_TILE = 0, PACK_ROWS = 1, PACK_FRAG = 2;
 
-// layout 3: [N/256][K/32][kstep 2][blk 8][split 2][lane 64][8] f16,
-// n = 256 ntile + 32 blk + (lane & 31), k = 32 piece + frag_channel(kstep, lane >> 5, j)
-__global__ void gemm_pack_frag_kernel(int N, int K, int sw, const float *__restrict__ W,
-                                      _Float16 *__restrict__ packed) {
+template <int LAYOUT>
+__global__ void gemm_pack_kernel(int N, int K, int sw, const float *__restrict__ W, _Float16 *__restrict__ packed) {
   const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const size_t total = (size_t)N * K * 2;
   if (e >= total) return;
   const int j = e & 7;
   const int lane = (e >> 3) & 63;
   const int split = (e >> 9) & 1;
-  const int blk = (e >> 10) & 7;
-  const int kstep = (e >> 13) & 1;
-  const size_t rest = e >> 14;
-  const int piece = (int)(rest % (K / RK));
-  const int ntile = (int)(rest / (K / RK));
-  const int n = ntile * RN + blk * 32 + (lane & 31);
-  const int k = piece * RK + frag_channel(kstep, lane >> 5, j);
+  int n, k;
+  if (LAYOUT == PACK_TILE) {
+    const int ks = (e >> 10) & 1;
+    const int nb = (e >> 11) & 3;
+    const size_t rest = e >> 13;
+    const int kiter = (int)(rest % (K / BK));
+    const int ntile = (int)(rest / (K / BK));
+    n = ntile * BN + nb * 32 + (lane & 31);
+    k = kiter * BK + ks * 16 + 8 * (lane >> 5) + j;
+  } else {
+    const int blk = (e >> 10) & 7;
+    const int kstep = (e >> 13) & 1;
+    const size_t rest = e >> 14;
+    const int piece = (int)(rest % (K / RK));
+    const int ntile = (int)(rest / (K / RK));
+    n = ntile * RN + blk * 32 + (lane & 31);
+    k = LAYOUT == PACK_FRAG ? piece * RK + frag_channel(kstep, lane >> 5, j) : piece * RK + 16 * (lane >> 5) + 8 * kstep + j;
+  }
   const float w = ldexpf(W[(size_t)n * K + k], sw);
   packed[e] = weight_half(w, split);
-}
-
-// (hi, lo) words of two scaled values, the remainder by plain subtraction (v_cvt_f32_f16 + v_sub_f32) where
-// split_f16.h's split2 issues one mixed-precision fma: same values, another instruction stream -- this file keeps the
-// one its kernels were measured and audited with (so do store_a and conv_slice above, and pos_embed.hip's frag kernel)
-__device__ __forceinline__ void split2_sub(float a0, float a1, unsigned &hw, unsigned &lw) {
-  const half2v h2 = __builtin_bit_cast(half2v, __builtin_amdgcn_cvt_pkrtz(a0, a1));
-  const float r0 = a0 - (float)h2[0], r1 = a1 - (float)h2[1];
-  hw = __builtin_bit_cast(unsigned, h2);
-  lw = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(r0, r1));
 }
 
 // fp32 rows -> frag rows (relu optional; values scaled by 2^sa).  One thread = one lane of one block.
@@ -657,7 +601,7 @@ __global__ __launch_bounds__(256) void rows_to_frag_kernel(int M, int C, const f
   if (u >= (size_t)(M / 32) * kbs) return;
   const int rb = (int)(u / kbs), kb = (int)(u % kbs);
   const float *row = x + (size_t)(32 * rb + (lane & 31)) * ldx + 32 * kb + 4 * (lane >> 5);
-  unsigned char *dst = out + (size_t)rb * rb_stride + (size_t)kb * FRAG_BLOCK_BYTES + lane * 16;
+  unsigned char *dst = frag_block(out, rb, rb_stride, kb, lane);
   unsigned amax16 = 0u;
 #pragma unroll
   for (int s = 0; s < 2; ++s) {
@@ -673,10 +617,9 @@ __global__ __launch_bounds__(256) void rows_to_frag_kernel(int M, int C, const f
         amax16 = amax_u16(amax16, hw[2 * q + e / 2], false);
       }
     }
-    *reinterpret_cast<u32x4 *>(dst + s * 2048) = u32x4{hw[0], hw[1], hw[2], hw[3]};
-    *reinterpret_cast<u32x4 *>(dst + s * 2048 + 1024) = u32x4{lw[0], lw[1], lw[2], lw[3]};
+    frag_store_kstep(dst, s, hw, lw);
   }
-  flag_f16_range(amax16, status, 4u);
+  flag_f16_range(amax16, status, RFD_STATUS_GEMM_RANGE);
 }
 
 // frag rows -> fp32 rows: (hi + lo) 2^-sa (exact: 22 significant bits)
@@ -689,11 +632,11 @@ __global__ __launch_bounds__(256) void frag_to_rows_kernel(int M, int C, const u
   if (u >= (size_t)(M / 32) * kbs) return;
   const int rb = (int)(u / kbs), kb = (int)(u % kbs);
   float *row = x + (size_t)(32 * rb + (lane & 31)) * ldx + 32 * kb + 4 * (lane >> 5);
-  const unsigned char *src = in + (size_t)rb * rb_stride + (size_t)kb * FRAG_BLOCK_BYTES + lane * 16;
+  const unsigned char *src = frag_block(in, rb, rb_stride, kb, lane);
 #pragma unroll
   for (int s = 0; s < 2; ++s) {
-    const half8 hi = *reinterpret_cast<const half8 *>(src + s * 2048);
-    const half8 lo = *reinterpret_cast<const half8 *>(src + s * 2048 + 1024);
+    const half8 hi = *reinterpret_cast<const half8 *>(src + frag_run(s, 0));
+    const half8 lo = *reinterpret_cast<const half8 *>(src + frag_run(s, 1));
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
       f32x4 v;
@@ -708,7 +651,7 @@ __global__ __launch_bounds__(256) void frag_to_rows_kernel(int M, int C, const u
 // (bias + gbias) 2^(sa+sw)), so an element is relu(acc) 2^-sw -> (hi, lo) -> four 1-KiB runs per 32 x 32 block, straight
 // from the registers: no loads, no LDS.
 __device__ __forceinline__ void frag_epilogue(const Args &g, const f32x16 (&acc)[8], int rb, int lane, int n0) {
-  unsigned char *dst = g.Cf + (size_t)rb * g.cf_stride + (size_t)(n0 / 32) * FRAG_BLOCK_BYTES + lane * 16;
+  unsigned char *dst = frag_block(g.Cf, rb, g.cf_stride, n0 / 32, lane);
   const float post = g.out_scale * g.a_scale;                 // 2^-sw
   unsigned amax16 = 0u;
 #pragma unroll
@@ -720,14 +663,10 @@ __device__ __forceinline__ void frag_epilogue(const Args &g, const f32x16 (&acc)
       split2_sub((a0 > 0.f ? a0 : 0.f) * post, (a1 > 0.f ? a1 : 0.f) * post, hw[w], lw[w]);
       amax16 = amax_u16(amax16, hw[w], true);
     }
-    unsigned char *d = dst + b * FRAG_BLOCK_BYTES;
-    *reinterpret_cast<u32x4 *>(d) = u32x4{hw[0], hw[1], hw[2], hw[3]};
-    *reinterpret_cast<u32x4 *>(d + 1024) = u32x4{lw[0], lw[1], lw[2], lw[3]};
-    *reinterpret_cast<u32x4 *>(d + 2048) = u32x4{hw[4], hw[5], hw[6], hw[7]};
-    *reinterpret_cast<u32x4 *>(d + 3072) = u32x4{lw[4], lw[5], lw[6], lw[7]};
+    frag_store(dst + b * FRAG_BLOCK_BYTES, hw, lw);
   }
   // cvt_pkrtz saturates at 65504 = 0x7bff: a stored hi word that large means the value left the f16 range
-  flag_f16_range(amax16, g.status, 4u);
+  flag_f16_range(amax16, g.status, RFD_STATUS_GEMM_RANGE);
 }
 
 // Row-owner GEMM on frag rows, PERSISTENT: one workgroup per CU walks its list of 256 x 256 tiles (same n tile, so the
@@ -797,6 +736,9 @@ __global__ __launch_bounds__(512) void gemm_rowsf_kernel(Args g) {
   f32x4 cbv[2];
   const unsigned char *xp;
 
+  // the four runs of a block (hi, lo of k step 0; hi, lo of k step 1): the offsets are text in the load strings
+  static_assert(frag_run(0, 0) == 0 && frag_run(0, 1) == 1024 && frag_run(1, 0) == 2048 && frag_run(1, 1) == 3072,
+                "load_k0 / load_k1 spell out frag_rows.h's run offsets");
   auto load_k0 = [&](int slot) {
     asm volatile("global_load_dwordx4 %0, %2, off\n\tglobal_load_dwordx4 %1, %2, off offset:1024"
                  : "=&v"(F[slot][0]), "=&v"(F[slot][1]) : "v"(xp) : "memory");
@@ -971,26 +913,30 @@ __global__ __launch_bounds__(512) void gemm_rowsf_kernel(Args g) {
   wait_vm<0>();                       // the last tile's look-ahead transfers: nothing may be in flight at s_endpgm
 }
 
+#undef XCD_TILE_MAP
+
 }  // namespace
 
-// two layouts: the 128 x 128 tile stream, then (for N % 256 == 0, K % 128 == 0) the row-owner stream
-// three layouts: tile stream, row-owner stream (fp32 rows), row-owner stream in frag k order
+// three layouts (gemm_pack_kernel): tile stream, row-owner stream (fp32 rows), row-owner stream in frag k order
 RFD_API size_t rfd_gemm_packed_bytes(int N, int K) { return (size_t)N * K * 2 * sizeof(_Float16) * 3; }
+
+// layout LAYOUT is the LAYOUT-th third of the packed buffer
+template <int LAYOUT>
+static int launch_pack(int N, int K, int sw, const float *W, void *packed, void *stream) {
+  const size_t total = (size_t)N * K * 2;
+  hipLaunchKernelGGL(gemm_pack_kernel<LAYOUT>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                     N, K, sw, W, (_Float16 *)packed + LAYOUT * total);
+  RFD_CHECK_LAUNCH();
+  return 0;
+}
 
 // W [N][K] fp32 (device) -> packed (device).  N % 128 == 0, K % 32 == 0.
 RFD_API int rfd_gemm_pack_w(int N, int K, int sw, const float *W, void *packed, void *stream) {
   if (N % BN || K % BK) { rfd_set_error("rfd_gemm_pack_w: N % 128 or K % 32", hipErrorInvalidValue); return (int)hipErrorInvalidValue; }
-  const size_t total = (size_t)N * K * 2;
-  hipLaunchKernelGGL(gemm_pack_w_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
-                     (hipStream_t)stream, N, K, sw, W, (_Float16 *)packed);
-  RFD_CHECK_LAUNCH();
-  if (N % RN == 0 && K % 128 == 0) {
-    hipLaunchKernelGGL(gemm_pack_rows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
-                       (hipStream_t)stream, N, K, sw, W, (_Float16 *)packed + total);
-    RFD_CHECK_LAUNCH();
-    hipLaunchKernelGGL(gemm_pack_frag_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
-                       (hipStream_t)stream, N, K, sw, W, (_Float16 *)packed + 2 * total);
-    RFD_CHECK_LAUNCH();
+  if (int rc = launch_pack<PACK_TILE>(N, K, sw, W, packed, stream)) return rc;
+  if (N % RN == 0 && K % 128 == 0) {                 // the shapes the row-owner kernels take
+    if (int rc = launch_pack<PACK_ROWS>(N, K, sw, W, packed, stream)) return rc;
+    if (int rc = launch_pack<PACK_FRAG>(N, K, sw, W, packed, stream)) return rc;
   }
   return 0;
 }
@@ -1019,21 +965,15 @@ RFD_API int rfd_gemm_f16x3(int M, int N, int K, const float *A, int lda, const v
   g.pool = pool_max;
   g.pool_signed = pool_signed;
   g.gbias_stride = N;
-  RfdWorkspace *ws0;
-  {
-    int rc0 = rfd_get_workspace(&ws0);
-    if (rc0) return rc0;
-  }
-  g.status = rfd_status_word(ws0, (hipStream_t)stream);
+  RfdWorkspace *ws;
+  if (int rc = rfd_get_workspace(&ws)) return rc;
+  g.status = rfd_status_word(ws, (hipStream_t)stream);
   // RFD_GEMM_TILE_ONLY: A/B switch of tools/gemm_bench.py (the tile kernel for every shape), read once per process
   static const bool tile_only = getenv("RFD_GEMM_TILE_ONLY") != nullptr;
   const bool aligned = !(ldc & 3) && !(ldr & 3) && !((uintptr_t)C & 15) && !((uintptr_t)R & 15) &&
                        !((uintptr_t)bias & 15) && !((uintptr_t)gbias & 15);
   if (M % RM == 0 && N % RN == 0 && N <= RFD_ZEROS_FLOATS && K % 128 == 0 && aligned &&
       ((!gbias && !pool_max) || g.rows_per_group % 64 == 0) && !tile_only) {
-    RfdWorkspace *ws;
-    int rc = rfd_get_workspace(&ws);
-    if (rc) return rc;
     if (!g.bias) g.bias = ws->zeros;
     if (!g.gbias) {
       g.gbias = ws->zeros;       // every group reads the same zero vector
@@ -1057,8 +997,8 @@ RFD_API int rfd_gemm_f16x3(int M, int N, int K, const float *A, int lda, const v
   return 0;
 }
 
-// ---- frag rows (see "Fragment-ordered split activations" above) ------------------------------------------------
-// bytes of a frag buffer of M rows x C channels (M % 32 == 0, C % 32 == 0): [M/32][C/32][4096]
+// ---- frag rows (see "Fragment-ordered split activations" above): a buffer of M rows x C channels (M % 32 == 0,
+// C % 32 == 0) is [M/32][C/32][FRAG_BLOCK_BYTES] ------------------------------------------------------------------
 
 // x [M][ldx] fp32 -> frag rows of relu?(x) 2^sa.  out = first block of row block 0, rb_stride = bytes between row blocks.
 RFD_API int rfd_rows_to_frag(int M, int C, const float *x, int ldx, int relu, int sa, void *out, long rb_stride,

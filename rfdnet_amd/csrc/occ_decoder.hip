@@ -410,7 +410,7 @@ __global__ __launch_bounds__(256) void occ_decode_kernel(
   part += __shfl_xor(part, 32);
   if (half == 0) logits[pidx] = part + fc_out_b;
   }  // persistent tile loop
-  flag_f16_range(amax16, status, 2u);
+  flag_f16_range(amax16, status, RFD_STATUS_DECODER_RANGE);
 }
 
 }  // namespace

@@ -459,7 +459,7 @@ __global__ __launch_bounds__(512) void occ_decode8_kernel(
     if (!claim) break;
     next_chunk(t_begin, t_end);
   }
-  flag_f16_range(amax16, status, 2u);
+  flag_f16_range(amax16, status, RFD_STATUS_DECODER_RANGE);
   if (claim) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the last tile's unused ring prefetch has landed
     if (tid() == 0) {

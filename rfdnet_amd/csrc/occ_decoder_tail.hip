@@ -178,7 +178,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
       logits[pidx] = part + fc_out_b;
     }
   }
-  flag_f16_range(amax16, status, 2u);
+  flag_f16_range(amax16, status, RFD_STATUS_DECODER_RANGE);
 }
 
 }  // namespace

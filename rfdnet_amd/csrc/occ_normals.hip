@@ -6,9 +6,10 @@
 // accumulation).  The conversion, the range watch and the S / T fetch are split_f16.h's, the k-step product and the
 // weight-fragment ring occ_wave16.h's, shared with that file.
 //
-// Forward pass: the decoder exactly as the tail kernel evaluates it (same table, same packed stream, same status bit 2 on an
-// activation beyond the f16 range), but nothing is kept of it except the ReLU masks of its 11 CBN layers.  In the D layout a
-// lane holds 64 channels of each layer, so a mask is 64 bits; bit 8 s + j belongs to the channel in slot j of k-step s's B
+// Forward pass: the decoder exactly as the tail kernel evaluates it (same table, same packed stream, same
+// RFD_STATUS_DECODER_RANGE on an activation beyond the f16 range), but nothing is kept of it except the ReLU masks of its
+// 11 CBN layers.  In the D layout a lane holds 64 channels of each layer, so a mask is 64 bits; bit 8 s + j belongs to
+// the channel in slot j of k-step s's B
 // fragment (channel 32 s + 16 (j >> 2) + 4 kg + (j & 3)) -- the same slot the backward pass reads it from.  The ten block masks
 // travel through a register queue (shifted once per block: static indices, no scratch).
 //
@@ -25,7 +26,7 @@
 // after every block the point's max |g'| over its 256 channels (4 lanes) is brought into [1, 2) by a power of two (exact), so
 // the f16 (hi, lo) parts neither overflow nor lose the lo part to underflow; 2^X comes back in fp32 at the end (X starts at KH
 // and fc_p_w = W_p 2^KH: the two cancel).  An f16 split beyond the range anyway (a gradient that grows by > 2^15 inside one
-// block) raises status bit 2 like an activation.
+// block) raises RFD_STATUS_DECODER_RANGE like an activation.
 // Outputs: normals[v] = -g / |g| (fp32); where g is exactly zero that is 0/0 = NaN, as in the reference (torch autograd's
 // ni / torch.norm(ni)).  grad (optional) = g.
 //
@@ -348,7 +349,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
       grad[(size_t)v * 3 + 2] = ldexpf(d2, X);
     }
   }
-  flag_f16_range(amax16, status, 2u);
+  flag_f16_range(amax16, status, RFD_STATUS_DECODER_RANGE);
 }
 
 }  // namespace

@@ -296,9 +296,9 @@ __global__ __launch_bounds__(512) void chain_kernel(ChainArgs a) {
     a.out[(size_t)prop * c3 + c] = o;
     // the pooled feature is the next split-precision layer's INPUT (STN fc1, PointSeg's conv1 share): watch what is
     // stored, like the row-owner GEMM's pool path does -- |o| 2^sa beyond f16 would saturate there silently
-    if (fabsf(o) * a.ascale >= 65504.f) atomicOr(a.status, 4u);
+    flag_out_range(fabsf(o), a.ascale, a.status, RFD_STATUS_GEMM_RANGE);
   }
-  flag_f16_range(amax16, a.status, 4u);
+  flag_f16_range(amax16, a.status, RFD_STATUS_GEMM_RANGE);
 }
 
 // =====================================================================================================================
@@ -517,7 +517,7 @@ __global__ __launch_bounds__(512) void head_kernel(HeadArgs a) {
       if (a.n_cls > 1) a.out[row * a.n_cls + 1] = sc1 + s_bd[1];
     }
   }
-  flag_f16_range(amax16, a.status, 4u);
+  flag_f16_range(amax16, a.status, RFD_STATUS_GEMM_RANGE);
 }
 
 }  // namespace

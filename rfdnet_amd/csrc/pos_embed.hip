@@ -10,11 +10,11 @@
 // buffer the encoder's first GEMM reads; the torch composition (K = d GEMM + addcmul_) moved
 // three times as many bytes.
 #include "common.h"
-#include "split_f16.h"
+#include "frag_rows.h"
 
 namespace {
 
-using namespace split_f16;
+using namespace frag_rows;
 
 constexpr int PE_THREADS = 256;
 constexpr int PE_MAX_D = 8;
@@ -57,11 +57,11 @@ __global__ __launch_bounds__(PE_THREADS) void pos_embed_kernel(
   }
   // the consumer is a split-precision GEMM (csrc/gemm_f16x3.hip, activations scaled by 2^sa before
   // the f16 split): a value beyond 65504 / 2^sa would be silently saturated there -- say so
-  if (omax * next_scale >= 65504.f) atomicOr(status, 4u);
+  flag_out_range(omax, next_scale, status, RFD_STATUS_GEMM_RANGE);
 }
 
 
-// ---- the same layer, written as frag rows (csrc/gemm_f16x3.hip "Fragment-ordered split activations") -----------
+// ---- the same layer, written as frag rows (csrc/frag_rows.h) --------------------------------------------------
 // out block (rb, kb) = relu(out[32 rb .. +31][32 kb .. +31]) 2^sa split into f16 (hi, lo), in the channel order of
 // the consumer's matrix instruction.  A wave owns a 32-row block at a time and walks its N / 32 channel blocks; lane
 // (row, half) produces the 16 channels of its row the block assigns to it.  W[:, :d] and the bias sit in LDS (all
@@ -87,7 +87,7 @@ __global__ __launch_bounds__(PE_THREADS) void pos_embed_frag_kernel(
     for (int j = 0; j < D; ++j) xr[j] = x[(size_t)r * ldx + j];
     const float m = mask[r];
     const float *grow = group + (size_t)(r / rows_per_group) * N + 4 * half;
-    unsigned char *dst = out + (size_t)rb * rb_stride + lane * 16;
+    unsigned char *dst = frag_block(out, rb, rb_stride, 0, lane);
     for (int kb = 0; kb < kbs; ++kb) {
       unsigned hw[8], lw[8];
 #pragma unroll
@@ -106,22 +106,14 @@ __global__ __launch_bounds__(PE_THREADS) void pos_embed_frag_kernel(
         }
 #pragma unroll
         for (int e = 0; e < 4; e += 2) {
-          const half2v h2 = __builtin_bit_cast(half2v, __builtin_amdgcn_cvt_pkrtz(o[e], o[e + 1]));
-          const float r0 = o[e] - (float)h2[0], r1 = o[e + 1] - (float)h2[1];
-          const unsigned h = __builtin_bit_cast(unsigned, h2);
-          hw[2 * q + e / 2] = h;
-          lw[2 * q + e / 2] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(r0, r1));
-          amax16 = pk_max_u16(amax16, h);
+          split2_sub(o[e], o[e + 1], hw[2 * q + e / 2], lw[2 * q + e / 2]);
+          amax16 = pk_max_u16(amax16, hw[2 * q + e / 2]);
         }
       }
-      unsigned char *d = dst + (size_t)kb * 4096;
-      *reinterpret_cast<u32x4 *>(d) = u32x4{hw[0], hw[1], hw[2], hw[3]};
-      *reinterpret_cast<u32x4 *>(d + 1024) = u32x4{lw[0], lw[1], lw[2], lw[3]};
-      *reinterpret_cast<u32x4 *>(d + 2048) = u32x4{hw[4], hw[5], hw[6], hw[7]};
-      *reinterpret_cast<u32x4 *>(d + 3072) = u32x4{lw[4], lw[5], lw[6], lw[7]};
+      frag_store(dst + (size_t)kb * FRAG_BLOCK_BYTES, hw, lw);
     }
   }
-  flag_f16_range(amax16, status, 4u);          // hi words are non-negative
+  flag_f16_range(amax16, status, RFD_STATUS_GEMM_RANGE);          // hi words are non-negative
 }
 
 }  // namespace

@@ -145,8 +145,8 @@ RFD_API int rfd_release_stream(void *stream) {
 // A launch whose G workgroups cannot all be resident (a CU-masked stream, a partitioned GPU, somebody else's
 // persistent kernel holding the CUs) can never finish its first exchange; the reference's behaviour for a launch
 // that cannot run is to fail fast (cuda_utils.h:30-39).  A workgroup that has polled `ms` for one round's
-// candidates raises the launch's sticky abort word: every workgroup -- running or started later -- leaves, status
-// bit 0 is set and the host raises.  Returns the previous value; ms <= 0 restores the default.
+// candidates raises the launch's sticky abort word: every workgroup -- running or started later -- leaves,
+// RFD_STATUS_FPS_ABORT is set and the host raises.  Returns the previous value; ms <= 0 restores the default.
 RFD_API int rfd_fps_set_timeout_ms(int ms) {
   RfdWorkspace *ws;
   if (rfd_get_workspace(&ws)) return -1;

@@ -14,7 +14,7 @@
 //       atomics; the data is its own flag) -> every wave picks the winner.
 // A launch whose G workgroups are not all resident can never complete an exchange.  It does not hang: a wave
 // that has polled for longer than the launch's time-out raises the region's sticky abort word, every workgroup
-// (polling, or dispatched only later) sees it and leaves the round loop, and status bit 0 tells the host
+// (polling, or dispatched only later) sees it and leaves the round loop, and RFD_STATUS_FPS_ABORT tells the host
 // (the reference's launch that cannot run fails fast too, cuda_utils.h:30-39).
 // HBM traffic is the algorithmic minimum: 12 B/point in, 4 B/point (temp) +
 // 4 B/sample out.
@@ -248,7 +248,7 @@ __global__ __launch_bounds__(FPS_THREADS) void fps_kernel(
             if (dead || now - t_first > timeout_ticks) {
               if (lane == 0) {
                 __hip_atomic_store(abort_word, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                atomicOr(status, 1u);
+                atomicOr(status, RFD_STATUS_FPS_ABORT);
                 s_abort = 1;
               }
               break;  // this round's "winner" is garbage; everybody reads the flag behind the barrier below

@@ -38,9 +38,17 @@ __device__ __forceinline__ unsigned pk_max_u16(unsigned a, unsigned b) {
   return r;
 }
 // 0x7bff = 65504 = the largest finite f16: the round-to-zero conversion saturates there, so a |hi| word that large
-// means a value left the f16 range -> `bit` of the status word (2: decoder activations, 4: GEMM / chain operands)
-__device__ __forceinline__ void flag_f16_range(unsigned amax16, unsigned *status, unsigned bit) {
-  if ((amax16 & 0xffffu) >= 0x7bffu || (amax16 >> 16) >= 0x7bffu) atomicOr(status, bit);
+// means a value left the f16 range -> `flag` of the status word (include/rfd_pointnet2.h: RFD_STATUS_DECODER_RANGE for
+// decoder activations, RFD_STATUS_GEMM_RANGE for GEMM / chain operands)
+__device__ __forceinline__ void flag_f16_range(unsigned amax16, unsigned *status, unsigned flag) {
+  if ((amax16 & 0xffffu) >= 0x7bffu || (amax16 >> 16) >= 0x7bffu) atomicOr(status, flag);
+}
+// the same watch on a value a kernel STORES in fp32 for the next split-precision layer, which will scale it by
+// `next_scale` (2^sa) before its own split: |v| 2^sa >= F16_MAX would saturate there silently
+constexpr float F16_MAX = 65504.f;
+__device__ __forceinline__ bool out_of_f16_range(float absmax, float next_scale) { return absmax * next_scale >= F16_MAX; }
+__device__ __forceinline__ void flag_out_range(float absmax, float next_scale, unsigned *status, unsigned flag) {
+  if (out_of_f16_range(absmax, next_scale)) atomicOr(status, flag);
 }
 
 // ---- the conversion -------------------------------------------------------------------------------------------------

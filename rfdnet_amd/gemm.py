@@ -12,7 +12,7 @@ import torch
 from . import _lib, occ_fold
 
 SA = 4            # activations scaled by 2^SA before the f16 split (|a| < 4094); lower_scale() -> SA_FALLBACK
-SA_FALLBACK = 1   # after an f16-range flag (status bit 4): |a| < 32752
+SA_FALLBACK = 1   # after an f16-range flag (_lib.STATUS_GEMM_RANGE): |a| < 32752
 _cache = _lib.ArtefactCache(256)      # weight -> (packed stream, weight exponent)
 
 
@@ -58,7 +58,7 @@ def linear(x, weight, bias=None, gbias=None, rows_per_group=1, residual=None, re
 
 
 def lower_scale():
-    """After status bit 4 (a stored activation * 2^SA reached the f16 limit): switch every split-precision GEMM of
+    """After STATUS_GEMM_RANGE (a stored activation * 2^SA reached the f16 limit): switch every split-precision GEMM of
     this process to the fallback scale, once.  True = run the stage again; False = already at the fallback scale."""
     global SA
     if SA <= SA_FALLBACK:
@@ -70,11 +70,15 @@ def lower_scale():
     return True
 
 
-def pool_usable(M, N, K, rows_per_group):
+def frag_usable(M, N, K, rows_per_group=64):
+    """shapes the row-owner kernels take: linear(pool=...) and rfd_gemm_f16x3_frag"""
     return M % 256 == 0 and N % 256 == 0 and K % 128 == 0 and rows_per_group % 64 == 0
 
 
-# ---- fragment-ordered split activations ("frag rows", csrc/gemm_f16x3.hip) -----------------------------------------
+pool_usable = frag_usable
+
+
+# ---- fragment-ordered split activations ("frag rows", csrc/frag_rows.h) --------------------------------------------
 # A frag buffer of M rows x C channels is an f16 tensor of shape (M/32, C/32, 2, 2, 64, 8) = [row block][channel block]
 # [k step][hi / lo][lane][8]: relu(x) * 2^sa split into f16 (hi, lo), in the operand order of the consumer's matrix
 # instruction.  A channel window is a slice of dim 1 (row-block stride = stride(0)), so [hidden | input] concatenations
@@ -93,11 +97,6 @@ def _frag_args(f):
     assert f.dtype == torch.float16 and f.shape[2:] == FRAG_SHAPE and f.stride()[1:] == (2048, 1024, 512, 8, 1), \
         "not a frag buffer (or not a plain channel window of one)"
     return f.data_ptr(), f.stride(0) * 2
-
-
-def frag_usable(M, N, K, rows_per_group=64):
-    """shapes rfd_gemm_f16x3_frag takes"""
-    return M % 256 == 0 and N % 256 == 0 and K % 128 == 0 and rows_per_group % 64 == 0
 
 
 def rows_to_frag(x, sa=None, relu=True, out=None):

@@ -306,7 +306,7 @@ class Generator3D(object):
         offsets, fold = (table, fc_p_w) of the K codes.  -> refined vertices (V,3) f32 (a new tensor: v is the kept v0)
         [, the first step's vertex gradient (V,3) f32].  eps: the weights, (steps, F, 3), instead of a draw (set_refinement's
         eps_source).  Every mesh has its own loss (its own means) and its own RMSprop state, as in the reference's per-object
-        loop; empty meshes take no part.  Asynchronous, no host round trip inside the loop: the f16-range flag (status bit 2)
+        loop; empty meshes take no part.  Asynchronous, no host round trip inside the loop: the f16-range flag (STATUS_DECODER_RANGE)
         is left in the stream's status word for the caller's run_with_range_fallback, which starts again from v0."""
         dec = self.model.decoder
         if dec.mode != MODE_F16X3:

@@ -192,7 +192,7 @@ class ISCNet(nn.Module):
     def reconstruct(self, end_points, proposal_features, ids, pc, return_grids=False, hook=None):
         """skip propagation -> object codes -> occupancy completion for the selected proposals, with the status
         reads that must follow (see complete()).  A split-precision GEMM activation beyond the f16 range at the
-        default scale (status bit 4, skip-propagation encoder) does not fail the scene either: the stage is run
+        default scale (_lib.STATUS_GEMM_RANGE, skip-propagation encoder) does not fail the scene either: the stage is run
         again at the fallback scale (gemm.lower_scale), and only a second flag raises.
         hook(codes, cls): called before the completion (the benchmark installs its copy scheduling there)."""
         from .. import _lib, gemm
@@ -213,7 +213,7 @@ class ISCNet(nn.Module):
             try:
                 return self.complete(codes, cls, pc.device, return_grids=return_grids, before=snap)
             except _StageFlag as e:
-                if e.status & 4 and not e.status & ~4 and attempt == 0:
+                if e.status & _lib.STATUS_GEMM_RANGE and not e.status & ~_lib.STATUS_GEMM_RANGE and attempt == 0:
                     with _lib.BUILD_LOCK:
                         lowered = gemm.lower_scale()
                     # again when the scale came down -- by this scene, or by another scene in flight since this one

@@ -26,7 +26,7 @@ TILE = 128
 
 def run_with_range_fallback(dec, run, device, before=None):
     """out = run() (the fold and the launches) with the stream's status read that must follow it.  An activation beyond
-    the f16 range (status bit 2) does not fail the call: run() is called once more when the decoder's scale has come
+    the f16 range (_lib.STATUS_DECODER_RANGE) does not fail the call: run() is called once more when the decoder's scale has come
     down since the first run began -- by this call (dec.lower_activation_scale()), or by another host thread sharing
     the decoder (its run was folded at the OLD scale).  Only a flag raised at the fallback scale is a real overflow.
     before(): called after the status read and before the scale is looked at -- it raises for the flags of earlier
@@ -37,13 +37,13 @@ def run_with_range_fallback(dec, run, device, before=None):
         st = _lib.stream_status_bits()
     if before is not None:
         before()
-    if st & 2:
+    if st & _lib.STATUS_DECODER_RANGE:
         with _lib.BUILD_LOCK:
             lowered = dec.lower_activation_scale()
         if lowered or dec.ka < ka_used:
             out = run()
             with torch.cuda.device(device):
-                st = (st & ~2) | _lib.stream_status_bits()
+                st = (st & ~_lib.STATUS_DECODER_RANGE) | _lib.stream_status_bits()
     _lib.raise_status(st)
     return out
 
@@ -153,7 +153,7 @@ class DecoderCBatchNorm(nn.Module):
         Generator3D.estimate_normals, generator.py:200-224).
         verts (V,3) f64 device tensor (all meshes back to back), vend: K + 1 vertex offsets (list or sequence), table /
         fc_p_w: the fold of the meshes' codes (fold()).  -> normals (V,3) f32 [, grad (V,3) f32].  A vertex whose gradient
-        is exactly zero gets NaN (0/0, as in the reference).  Asynchronous: the f16-range flag (status bit 2) is left in
+        is exactly zero gets NaN (0/0, as in the reference).  Asynchronous: the f16-range flag (STATUS_DECODER_RANGE) is left in
         the stream's status word for the caller to read, like decode_tiles()."""
         if self.mode != MODE_F16X3:
             raise NotImplementedError("vertex normals need the parity mode (MODE_F16X3); MODE_F16X1 is not supported")
@@ -232,7 +232,7 @@ class DecoderCBatchNorm(nn.Module):
         return occ_fold.fold_table_stacked(_lib.build_once(self.__dict__, '_fold_cache', key, build, c.device), z, c)
 
     def lower_activation_scale(self):
-        """After status bit 2 (an activation * 2^ka reached the f16 limit): switch to the fallback scale, once.
+        """After STATUS_DECODER_RANGE (an activation * 2^ka reached the f16 limit): switch to the fallback scale, once.
         Returns True if the caller should run the launch again, False if the fallback scale is already in use
         (then the overflow is real: |activation| >= 8190)."""
         if self.ka <= occ_fold.KA_FALLBACK:

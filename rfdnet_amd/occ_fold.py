@@ -26,7 +26,7 @@ import math
 import torch
 
 KA = 6               # default activation scale 2^6: f16 lo parts stay normal down to |a| ~ 2^-9
-KA_FALLBACK = 3      # scale after an f16-range flag (status bit 2): activations up to 8190 instead of 1023
+KA_FALLBACK = 3      # scale after an f16-range flag (STATUS_DECODER_RANGE): activations up to 8190 instead of 1023
 BN_EPS = 1e-5
 N_BLOCKS = 5
 HIDDEN = 256

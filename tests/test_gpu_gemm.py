@@ -417,6 +417,67 @@ def test_frag_rows_round_trip_and_layout(hip):
     assert (gemm.frag_to_rows(gemm.rows_to_frag(x, sa=sa, relu=False), sa=sa) - x).abs().max().item() <= 2.0 ** -20 * 16
 
 
+def pack_w_weights(N, K, extra):
+    """(w, sw): fp32 weights with |w| 2^sw in [2^-3, 2^3] for sw = occ_fold.choose_kw([w]) + extra.  choose_kw never
+    exceeds 24, so the weights are that small: max |w| = 2^(3 - 24 - extra), an exact power of two that pins its value."""
+    rng = np.random.RandomState(1000 * extra + N + K)
+    mant = rng.uniform(1.0, 2.0, (N, K))
+    expo = rng.randint(-3, 3, (N, K))                                  # [2^-3, 2^3)
+    sign = rng.choice([-1.0, 1.0], (N, K))
+    w = (sign * mant * 2.0 ** expo).astype(np.float32)
+    w[N // 2, K // 2] = 8.0                                            # the maximum, exactly 2^3
+    return np.ldexp(w, -(24 + extra)).astype(np.float32), 24 + extra
+
+
+def pack_w_reference(w, sw):
+    """The three streams of rfd_gemm_pack_w as include/rfd_occ.h and csrc/gemm_f16x3.hip document them, as int16 bit
+    patterns; hi = float16(w 2^sw) (round to nearest even), lo = float16(float32(w 2^sw) - float32(hi))."""
+    N, K = w.shape
+    ws = np.ldexp(w, sw).astype(np.float32)                            # exact
+    hi = ws.astype(np.float16)
+    lo = (ws - hi.astype(np.float32)).astype(np.float16)               # the difference is exact in fp32
+    halves = np.stack([hi, lo]).view(np.int16)                         # [split][n][k]
+    # layout 1, the 128 x 128 tile kernel: [N/128][K/32][nb 4][kstep 2][split 2][lane 64][8]
+    nt, kit, nb, ks, split, lane, j = np.indices((N // 128, K // 32, 4, 2, 2, 64, 8))
+    tile = halves[split, 128 * nt + 32 * nb + (lane & 31), 32 * kit + 16 * ks + 8 * (lane >> 5) + j]
+    if N % 256 or K % 128:
+        return [tile.ravel()]
+    # layouts 2 and 3, the row-owner kernels: [N/256][K/32][kstep 2][blk 8][split 2][lane 64][8]
+    nt, piece, ks, blk, split, lane, j = np.indices((N // 256, K // 32, 2, 8, 2, 64, 8))
+    n = 256 * nt + 32 * blk + (lane & 31)
+    rows = halves[split, n, 32 * piece + 16 * (lane >> 5) + 8 * ks + j]
+    r = 8 * ks + j                                                     # frag rows: the accumulator order of 32x32x16
+    frag = halves[split, n, 32 * piece + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)]
+    return [tile.ravel(), rows.ravel(), frag.ravel()]
+
+
+@pytest.mark.parametrize("extra", [0, 3])
+@pytest.mark.parametrize("N,K", [(128, 32), (512, 256), (256, 160)])
+def test_pack_w_layouts(hip, N, K, extra):
+    """The packed weight stream itself, byte for byte: rfd_gemm_pack_w against a numpy restatement of the three
+    documented layouts and of the round-to-nearest (hi, lo) split.  (128, 32): the tile layout only; (512, 256): two
+    256-wide n tiles x eight k pieces, so a swapped tile / piece order or a wrong frag_channel shows; (256, 160):
+    K % 128 != 0, layouts 2 and 3 must stay unwritten (the buffer is pre-filled with a sentinel)."""
+    from rfdnet_amd import _lib, occ_fold
+    w, sw = pack_w_weights(N, K, extra)
+    wt = torch.from_numpy(w).cuda()
+    assert occ_fold.choose_kw([wt]) + extra == sw
+    scaled = np.abs(np.ldexp(w, sw))
+    assert scaled.min() >= 2.0 ** -3 and scaled.max() <= 2.0 ** 3
+    total = N * K * 2
+    assert _lib.lib().rfd_gemm_packed_bytes(N, K) == 3 * total * 2
+    sentinel = 0x5a5a                                                  # 203.25 as f16: no |w| 2^sw <= 8 packs to it
+    buf = torch.full((3 * total,), sentinel, dtype=torch.int16, device="cuda")
+    _lib.call("rfd_gemm_pack_w", wt.device, N, K, sw, wt.data_ptr(), buf.data_ptr())
+    torch.cuda.synchronize()
+    got = buf.cpu().numpy()
+    want = pack_w_reference(w, sw)
+    assert len(want) == (3 if (N, K) == (512, 256) else 1)
+    for layout, stream in enumerate(want):
+        np.testing.assert_array_equal(got[layout * total:(layout + 1) * total], stream, err_msg="layout %d" % (layout + 1))
+    assert (got[len(want) * total:] == sentinel).all()
+
+
 @pytest.mark.parametrize("M,N,K,T", [(256, 256, 128, 64), (512, 512, 384, 128), (2048, 512, 1024, 1024),
                                      # tile-list shapes of the persistent kernel: 9 m tiles (no XCD-aware list), three and
                                      # four n tiles (240 / 256 workgroups), more tiles than workgroups (3 tiles per workgroup)

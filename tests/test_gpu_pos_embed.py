@@ -77,7 +77,7 @@ def test_pos_embed_ragged_shapes_against_float64(hip, M, rpg, N, d, soft):
 
 
 def test_pos_embed_range_flag_at_a_ragged_shape(hip):
-    """status bit 2 (value 4) is raised when a stored value x 2^sa reaches 65504, the largest f16 -- and is clear
+    """RFD_STATUS_GEMM_RANGE is raised when a stored value x 2^sa reaches 65504, the largest f16 -- and is clear
     just below it -- also in the last, single-row block (M = 65) and the last columns of a short pass (N = 36)"""
     from rfdnet_amd import gemm, pos_embed
     M, rpg, N, d = 65, 65, 36, 3

@@ -91,7 +91,24 @@ def test_shipped_kernels_carry_no_wrong_result_switch_and_the_ablation_patch_reb
         if name != "split_f16.h":
             for token in ("v_pk_max_u16", "v_fma_mix_f32", "0x7bffu"):
                 assert token not in text, (name, token)
-    shipped = _asm(tmp_path, "occ_decoder8.hip", "dec8_shipped.s")
+            assert "65504.f" not in text, name                          # ... and so has the fp32 form of the limit
+        # the status flags are named (include/rfd_pointnet2.h): no bare 1u / 2u / 4u where one is raised
+        for m in re.finditer(r"\b(?:atomicOr|flag_f16_range|flag_out_range)\(([^;{]*)\);", text):
+            assert not re.search(r",\s*[124]u\s*$", m.group(1)), (name, m.group(0))
+        # the frag-rows block layout (4 KiB = four 1-KiB runs) is frag_rows.h's: its users spell no offset of it out,
+        # apart from the load strings of gemm_rowsf_kernel and the static_assert that ties them to the header
+        if '#include "frag_rows.h"' in text:
+            code = re.sub(r"//[^\n]*", "", text)
+            code = re.sub(r"static_assert\([^;]*;", "", code)
+            code = re.sub(r'"(?:[^"\\\n]|\\.)*"', '""', code)
+            assert not re.search(r"\+\s*1024\b|\b(?:2048|3072|4096)\b", code), name
+    users = [n for n in os.listdir(csrc) if '#include "frag_rows.h"' in open(os.path.join(csrc, n)).read()]
+    assert sorted(users) == ["gemm_f16x3.hip", "pos_embed.hip"], users
+    gemm_text = open(os.path.join(csrc, "gemm_f16x3.hip")).read()
+    assert re.search(r"static_assert\(frag_run\(0, 0\) == 0 && frag_run\(0, 1\) == 1024 && frag_run\(1, 0\) == 2048 && "
+                     r"frag_run\(1, 1\) == 3072", gemm_text)
+    assert "off offset:1024" in gemm_text and "off offset:2048" in gemm_text and "off offset:3072" in gemm_text
+    shipped =_asm(tmp_path, "occ_decoder8.hip", "dec8_shipped.s")
     patched = _asm(tmp_path, _ablation_source(tmp_path), "dec8_patched.s")
     assert _code_lines(shipped) == _code_lines(patched)
     # round 6: the same rule for the frag-rows GEMM's timing-only switches (AB_NOXLOAD, AB_NODMA, ...:
