@@ -35,7 +35,9 @@ def build_parser():
                     help="--mode test: .npz with the scan's ground-truth labels (center_label, heading_class_label, "
                          "heading_residual_label, size_class_label, size_residual_label, sem_cls_label, "
                          "box_label_mask); the scene then goes through ISCNet.evaluate and its box AP / recall at IoU "
-                         "0.25 and 0.5 are printed")
+                         "0.25 and 0.5 are printed.  If it also holds object_points, object_points_occ and "
+                         "object_voxels, the completion loss and the mean voxel IoU are printed too (needs a "
+                         "checkpoint with completion.encoder_latent.* to mean anything)")
     ap.add_argument("--mean_size_npz", type=str, default=None,
                     help="class mean sizes (the reference's datasets/scannet/scannet_means.npz); default: "
                          "$RFD_MEAN_SIZE_NPZ or that path relative to the working directory")
@@ -75,6 +77,11 @@ def main():
         cfg = Config({'generation': gen}, mean_size_arr=args.mean_size_npz)
     if args.allow_placeholder_sizes:
         cfg.eval_overrides['allow_placeholder_sizes'] = True
+    completion_keys = ('object_points', 'object_points_occ', 'object_voxels')
+    gt = np.load(args.gt) if args.mode == "test" and args.gt else None
+    completion = gt is not None and all(k in gt.files for k in completion_keys)
+    if completion:
+        cfg.config['data']['latent_encoder'] = True                      # before the weights are loaded: its keys are kept
     net = ISCNet(cfg)
     if args.weight:
         ckpt = torch.load(args.weight, map_location="cpu")
@@ -92,14 +99,17 @@ def main():
     torch.cuda.synchronize()
     t0 = time.time()
     records = None
-    if args.mode == "test" and args.gt:
-        gt = np.load(args.gt)
+    if gt is not None:
         for k in ('center_label', 'heading_class_label', 'heading_residual_label', 'size_class_label',
                   'size_residual_label', 'sem_cls_label', 'box_label_mask'):
             a = np.asarray(gt[k])
             per_scan = 2 if k in ('center_label', 'size_residual_label') else 1
             data[k] = torch.from_numpy(a[None] if a.ndim == per_scan else a).cuda()      # one scan: add the batch axis
-        end_points, ids, meshes, records = net.evaluate(data)
+        for k in completion_keys if completion else ():
+            a = np.asarray(gt[k], dtype=np.float32)
+            per_scan = 3 if k == 'object_points' else 2 if k == 'object_points_occ' else 4
+            data[k] = torch.from_numpy(a[None] if a.ndim == per_scan else a).cuda()
+        end_points, ids, meshes, records = net.evaluate(data, completion=completion)
     else:
         end_points, ids, meshes = net.generate(data, selection=args.selection)
     torch.cuda.synchronize()
@@ -110,6 +120,11 @@ def main():
         calc.step(records)
         for thr, metrics in zip((0.25, 0.5), calc.compute_metrics()):
             print('IoU %g: %s' % (thr, {k: float(v) for k, v in metrics.items()}))
+    if 'completion_loss' in end_points:
+        stats = end_points['iou_stats']
+        print('completion loss: %.4f; mean voxel IoU over %d proposals: %s'
+              % (float(end_points['completion_loss']), ids.shape[1],
+                 'n/a' if stats is None or not len(stats['iou']) else '%.4f' % float(np.nanmean(stats['iou']))))
     box = keep = None
     if 'parsed_predictions' in end_points:
         box = end_points['parsed_predictions']['box_params'][0].cpu().numpy()

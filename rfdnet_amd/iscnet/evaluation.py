@@ -349,3 +349,63 @@ def records_from_lists(batch_pred_map_cls, batch_gt_map_cls, ap_iou_thresh):
     counts = valid[:, 0].sum(1, dtype=np.int64)
     cls = np.repeat(np.array([k[1] for k in keys], np.int32), counts)
     return {'cls': cls, 'score': rec['score'], 'tp': rec['tp'], 'npos': npos, 'thr': thr}
+
+
+# ---- completion half of the test output (network.py:126-150, :387-471) ------------------------------------------------
+FAR_AWAY = 1.0e18        # where a masked-out ground-truth centroid is moved: squared distances stay finite in fp32
+
+
+@torch.no_grad()
+def proposal_to_gt(end_points, data, ids):
+    """The reference's BATCH_PROPOSAL_IDs (network.py:404-413, :433): ids (B,K',1) proposal ids -> (B,K',3) int64 rows
+    (proposal id, ground-truth box id, ground-truth class).  A proposal goes to the nearest ground-truth centroid among
+    the rows with box_label_mask set (nn_distance over the compacted centroids in the reference; here the Chamfer
+    nearest-neighbour kernel over all rows with the masked ones moved out of reach, so nothing waits for the host); a
+    tie goes to the lowest index.  A scene without any ground-truth box maps everything to row 0."""
+    from ..chamfer_distance import nearest
+    centers = end_points['center']
+    dev = centers.device
+    mask = data['box_label_mask'].to(dev) != 0
+    gt = data['center_label'].to(dev)[:, :, 0:3].float()
+    gt = torch.where(mask.unsqueeze(-1), gt, torch.full_like(gt, FAR_AWAY))
+    _, idx1, _, _ = nearest(centers, gt)
+    pid = ids[..., 0].long()
+    box = torch.gather(idx1.long(), 1, pid)
+    cls = torch.gather(data['sem_cls_label'].to(dev).long(), 1, box)
+    return torch.stack([pid, box, cls], dim=-1)
+
+
+@torch.no_grad()
+def prepare_data(data, proposal_ids):
+    """network.py:438-458: the ground-truth occupancy samples of every selected proposal's box:
+    data['object_points'] (B,G,T,3), data['object_points_occ'] (B,G,T), proposal_ids (B,K',3) ->
+    points (B*K',T,3), occupancies (B*K',T)."""
+    pts, occ = data['object_points'], data['object_points_occ']
+    B, G, T, D = pts.shape
+    Kp = proposal_ids.shape[1]
+    box = proposal_ids[:, :, 1].to(pts.device)
+    p = torch.gather(pts, 1, box.view(B, Kp, 1, 1).expand(B, Kp, T, D)).view(B * Kp, T, D)
+    o = torch.gather(occ, 1, box.view(B, Kp, 1).expand(B, Kp, T)).view(B * Kp, T)
+    return p, o
+
+
+@torch.no_grad()
+def voxel_iou(logits, logit_threshold, gt_voxels, return_counts=False):
+    """compute_iou (net_utils/libs.py) of the predicted voxels `logits >= logit_threshold` against `gt_voxels >= 0.5`:
+    logits (K,V) or (K,n,n,n) f32, gt_voxels the same shape (any dtype) -> iou (K,) f32 on the device =
+    inter.float() / union.float() from one rfd_voxel_iou launch; NaN for an empty pair, as numpy's 0 / 0."""
+    if not logits.is_cuda:
+        raise RuntimeError("CPU not supported")
+    K = logits.shape[0]
+    logits = logits.reshape(K, -1).float()
+    if logits.stride(-1) != 1 or (K > 1 and logits.stride(0) < logits.shape[1]):
+        logits = logits.contiguous()
+    V = logits.shape[1]
+    gt = gt_voxels.to(logits.device).reshape(K, -1).float().contiguous()
+    assert gt.shape == (K, V)
+    inter = torch.empty(K, dtype=torch.int32, device=logits.device)
+    union = torch.empty(K, dtype=torch.int32, device=logits.device)
+    _lib.call("rfd_voxel_iou", logits.device, K, V, logits.data_ptr(), int(logits.stride(0)) if K > 1 else V,
+              float(logit_threshold), gt.data_ptr(), inter.data_ptr(), union.data_ptr())
+    iou = inter.float() / union.float()
+    return (iou, inter, union) if return_counts else iou

@@ -154,8 +154,8 @@ class ISCNet(nn.Module):
         return fit.fit_mesh_to_scan(pred_mesh_dict['meshes'], pred_mesh_dict['proposal_ids'], parsed_predictions,
                                     eval_dict, input_scan, dump_threshold)
 
-    def generate(self, data, selection='all', return_grids=False):
-        """data['point_clouds'] (B,N,3+f) -> (end_points, proposal ids, meshes)."""
+    def generate(self, data, selection='all', return_grids=False, hook=None):
+        """data['point_clouds'] (B,N,3+f) -> (end_points, proposal ids, meshes).  hook: see reconstruct()."""
         pc = data['point_clouds']
         end_points, proposal_features = self.detect(pc)
         ids = self.select_proposals(end_points, selection, pc)
@@ -165,19 +165,29 @@ class ISCNet(nn.Module):
             from .. import _lib
             _lib.raise_status(_lib.stream_status_bits())
             return end_points, ids, []
-        out = self.reconstruct(end_points, proposal_features, ids, pc, return_grids=return_grids)
+        out = self.reconstruct(end_points, proposal_features, ids, pc, return_grids=return_grids, hook=hook)
         return end_points, ids, out
 
-    def evaluate(self, data, fit=True, ap_iou_thresh=(0.25, 0.5), timing=False):
+    def evaluate(self, data, fit=True, ap_iou_thresh=(0.25, 0.5), timing=False, completion=False, completion_eps=None):
         """The tail of the reference's `generate` in test mode (network.py:85-177): detection and completion with
         selection='nms', then (fit) the box refinement of fit_mesh_to_scan, then the evaluation records of the --
         refined -- boxes against the ground-truth labels in `data` (center_label, heading_class_label,
         heading_residual_label, size_class_label, size_residual_label, sem_cls_label, box_label_mask).
         -> (end_points, proposal ids, meshes, records): what generate returns plus evaluation.SceneRecords, queued on
         the current stream (feed them to evaluation.APCalculator.step).  end_points['parsed_predictions'] holds the
-        corners that were scored."""
+        corners that were scored.
+        completion=True adds the ground-truth-dependent completion block (network.py:126-150): `data` also carries
+        object_points (B,G,T,3), object_points_occ (B,G,T) and optionally object_voxels (B,G,16,16,16); every selected
+        proposal is paired with its nearest ground-truth box (evaluation.proposal_to_gt), that box's occupancy samples
+        are gathered (prepare_data) and ONet.compute_loss is run on them (completion_eps: its `eps`).  Results:
+        end_points['completion_loss'] (0-d device tensor), ['proposal_to_gt'] (B,K',3) and ['iou_stats'] =
+        {'cls','iou'} numpy arrays over the B*K' proposals (None without object_voxels).  The return tuple is the same."""
         from . import evaluation
-        end_points, ids, meshes = self.generate(data, selection='nms')
+        captured = {}
+        hook = (lambda codes, cls: captured.update(codes=codes, cls=cls)) if completion else None
+        end_points, ids, meshes = self.generate(data, selection='nms', hook=hook)
+        if completion:
+            self._completion_block(end_points, data, ids, captured, completion_eps)
         parsed = end_points['parsed_predictions']
         eval_dict = {'pred_mask': end_points['pred_mask']}
         if fit and len(meshes):
@@ -188,6 +198,31 @@ class ISCNet(nn.Module):
         records = evaluation.scene_records(eval_dict, parsed, parsed_gts, getattr(self.cfg, 'eval_overrides', None),
                                            ap_iou_thresh, timing=timing)
         return end_points, ids, meshes, records
+
+    @torch.no_grad()
+    def _completion_block(self, end_points, data, ids, captured, eps):
+        from . import evaluation
+        dev = end_points['center'].device
+        end_points['iou_stats'] = None
+        if ids.shape[1] == 0:
+            end_points['completion_loss'] = torch.zeros((), device=dev)
+            end_points['proposal_to_gt'] = ids.new_zeros(ids.shape[0], 0, 3)
+            return
+        pairs = evaluation.proposal_to_gt(end_points, data, ids)
+        on_dev = {k: data[k].to(dev) for k in ('object_points', 'object_points_occ')}
+        points, occ = evaluation.prepare_data(on_dev, pairs)
+        voxels = data.get('object_voxels')
+        loss, _, terms = self.completion.compute_loss(captured['codes'], points, occ, captured['cls'],
+                                                      export_shape=voxels is not None, eps=eps, return_terms=True)
+        end_points['completion_loss'] = loss
+        end_points['proposal_to_gt'] = pairs
+        if voxels is not None:
+            voxels = voxels.to(dev)
+            B, Kp = pairs.shape[:2]
+            box = pairs[:, :, 1].view(B, Kp, 1, 1, 1).expand(B, Kp, *voxels.shape[2:])
+            gt = torch.gather(voxels, 1, box).reshape(B * Kp, -1)
+            iou = evaluation.voxel_iou(terms['voxel_logits'], self.completion.logit_threshold(), gt)
+            end_points['iou_stats'] = {'cls': pairs[:, :, 2].reshape(-1).cpu().numpy(), 'iou': iou.cpu().numpy()}
 
     def reconstruct(self, end_points, proposal_features, ids, pc, return_grids=False, hook=None):
         """skip propagation -> object codes -> occupancy completion for the selected proposals, with the status

@@ -1,7 +1,8 @@
-"""Occupancy network wrapper (models/iscnet/modules/occupancy_net.py:12-189,
-generation path only): holds the decoder under the reference's attribute name
-(`decoder` => state_dict keys completion.decoder.*), the prior over z and the
-mesh generator."""
+"""Occupancy network wrapper (models/iscnet/modules/occupancy_net.py:12-189): holds the decoder under the reference's
+attribute name (`decoder` => state_dict keys completion.decoder.*), the prior over z, the mesh generator and -- once
+enable_latent_encoder() is called -- the latent encoder q(z | p, occ, c) with the completion loss of the test mode
+(compute_loss: KL + BCE + the 16^3 voxel example)."""
+import numpy as np
 import torch
 import torch.distributions as dist
 import torch.nn as nn
@@ -22,10 +23,15 @@ class ONet(nn.Module):
         base = data['c_dim'] if data['skip_propagate'] else 128
         c_dim = self.use_cls_for_completion * cfg.dataset_config.num_class + base
         self.threshold = data['threshold']
-        # the latent encoder q(z|p,occ,c) (encoder_latent.py) is training-only:
-        # generation uses the prior mean (occupancy_net.py:138-143)
+        # the latent encoder q(z|p,occ,c) (encoder_latent.py) serves compute_loss only -- the ground-truth-dependent
+        # completion loss of the reference's training AND test mode (network.py:140, testing.py:64); generation uses the
+        # prior mean (occupancy_net.py:138-143).  Opt-in (enable_latent_encoder / data.latent_encoder): the default
+        # state_dict is the decoder's alone.
+        self.c_dim = c_dim
         self.encoder_latent = None
         self.decoder = DecoderCBatchNorm(dim=3, z_dim=self.z_dim, c_dim=c_dim)
+        if data.get('latent_encoder'):
+            self.enable_latent_encoder()
         gen = cfg.config.get('generation')
         if gen and gen['generate_mesh']:
             self.generator = Generator3D(
@@ -36,6 +42,90 @@ class ONet(nn.Module):
                 preprocessor=None)
             if gen['refinement_step']:
                 self.generator.set_refinement(gen['refinement_step'])
+
+    def enable_latent_encoder(self):
+        """Attach the latent encoder (z_dim > 0; occupancy_net.py:40-43) in front of the decoder, so that state_dict()
+        is the reference ONet's full key list in its order and load_weight() keeps a checkpoint's
+        completion.encoder_latent.* tensors.  New parameters are initialised like nn.Linear's and live on the decoder's
+        device.  Call it before the network is shared (worker_view)."""
+        if self.z_dim == 0 or self.encoder_latent is not None:
+            return self
+        from .encoder_latent import Encoder_Latent
+        enc = Encoder_Latent(dim=3, z_dim=self.z_dim, c_dim=self.c_dim).to(self.decoder.fc_p.weight.device)
+        enc.train(self.training)
+        rest = dict(self._modules)
+        self.__dict__.pop('encoder_latent', None)
+        self._modules.clear()
+        self._modules['encoder_latent'] = enc
+        self._modules.update(rest)
+        return self
+
+    def infer_z(self, p, occ, c, device, **kwargs):
+        """-> q(z | p, occ, c) = Normal(mean, exp(logstd))  (occupancy_net.py:158-175)"""
+        if self.encoder_latent is not None:
+            mean_z, logstd_z = self.encoder_latent(p, occ, c, **kwargs)
+        else:
+            mean_z = torch.empty(p.size(0), 0, device=device)
+            logstd_z = torch.empty(p.size(0), 0, device=device)
+        return dist.Normal(mean_z, torch.exp(logstd_z))
+
+    def voxel_grid_points(self, device):
+        """the 16^3 lattice of compute_loss's shape example: make_3d_grid([-0.5 + 1/32] * 3, [0.5 - 1/32] * 3, (16,) * 3)
+        (external/common.py:157-176), x slowest"""
+        lin = torch.linspace(-0.5 + 1 / 32, 0.5 - 1 / 32, 16)
+        return torch.stack(torch.meshgrid(lin, lin, lin, indexing='ij'), dim=-1).view(-1, 3).to(device)
+
+    def logit_threshold(self):
+        """probs >= threshold as a comparison of logits (Generator3D.logit_threshold's conversion)"""
+        return float(np.log(self.threshold) - np.log(1. - self.threshold))
+
+    @torch.no_grad()
+    def compute_loss(self, input_features_for_completion, input_points_for_completion,
+                     input_points_occ_for_completion, cls_codes_for_completion, export_shape=False, eps=None,
+                     return_terms=False):
+        """The completion loss of occupancy_net.py:59-109 as an evaluation quantity (no gradient):
+        features (K,D), points (K,T,3), occupancies (K,T), class codes (K,C) -> (loss, voxels_out):
+        loss = mean_k KL(q(z|p,occ,c) || N(0,1)) + mean_k sum_t BCE-with-logits(decode(p, z, c), occ), z = q.rsample();
+        voxels_out (K,16,16,16) bool with export_shape (the decoder at the prior mean on the 16^3 lattice, thresholded),
+        else None.
+        eps (K, z_dim): the standard-normal draw of rsample (z = mean + exp(logstd) eps).  None draws torch.randn on the
+        device: the reference's distribution, but another stream than its CPU draw -- pass eps to reproduce a run.
+        return_terms: a third value {'kl','bce' (K,), 'mean','logstd','z' (K,z_dim), 'voxel_logits' (K,4096) or None}.
+        Launches: 5 (encoder) + the decoder's forward + 1 (BCE row sums) + a few elementwise torch ops."""
+        feat, p, occ = input_features_for_completion, input_points_for_completion, input_points_occ_for_completion
+        if self.z_dim > 0 and self.encoder_latent is None:
+            raise RuntimeError("ONet.compute_loss needs the latent encoder (z_dim = %d): call enable_latent_encoder() "
+                               "(or set data.latent_encoder) and load its weights" % self.z_dim)
+        if not (feat.is_cuda and p.is_cuda and occ.is_cuda):
+            raise RuntimeError("CPU not supported")
+        device = feat.device
+        K = feat.size(0)
+        if self.use_cls_for_completion:
+            feat = torch.cat([feat, cls_codes_for_completion.to(device).float()], dim=-1)
+        feat = feat.float()
+        occ = occ.contiguous().float()
+        terms = {'kl': None, 'mean': None, 'logstd': None, 'voxel_logits': None}
+        if self.z_dim > 0:
+            if eps is None:
+                eps = torch.randn(K, self.z_dim, device=device)
+            mean, logstd, z, kl = self.encoder_latent.posterior(p, occ, feat, eps.to(device))
+            loss = kl.mean()
+            terms.update(kl=kl, mean=mean, logstd=logstd)
+        else:
+            z = torch.empty(K, 0, device=device)
+            loss = 0.
+        logits = self.decode(p, z, feat).logits
+        bce = bce_logits_rowsum(logits, occ)
+        loss = loss + bce.mean()
+        terms.update(bce=bce, z=z)
+        voxels_out = None
+        if export_shape:
+            grid = self.voxel_grid_points(device)
+            z0 = self.get_z_from_prior((K,), device, sample=False)
+            vlogits = self.decode(grid.expand(K, *grid.size()), z0, feat).logits
+            voxels_out = (vlogits >= self.logit_threshold()).view(K, 16, 16, 16)
+            terms['voxel_logits'] = vlogits
+        return (loss, voxels_out, terms) if return_terms else (loss, voxels_out)
 
     def get_prior_z(self, z_dim, device):
         return dist.Normal(torch.zeros(z_dim, device=device), torch.ones(z_dim, device=device))
@@ -60,3 +150,25 @@ class ONet(nn.Module):
                 [input_features_for_completion, cls_codes_for_completion.to(device).float()], dim=-1)
         z = self.get_z_from_prior((input_points_for_completion.size(0),), device, sample=sample)
         return self.decode(input_points_for_completion, z, input_features_for_completion, **kwargs)
+
+
+def bce_logits_rowsum(logits, target):
+    """(K,T) f32 device tensors (unit stride along T) -> (K,) f32: sum_t binary_cross_entropy_with_logits, one
+    rfd_bce_logits_rowsum launch (f64 row sums in a fixed order: deterministic)"""
+    from .. import _lib
+    if not (logits.is_cuda and target.is_cuda):
+        raise RuntimeError("CPU not supported")
+    K, T = logits.shape
+    assert target.shape == (K, T) and logits.dtype == torch.float32 and target.dtype == torch.float32
+    if T > 1 and logits.stride(1) != 1:
+        logits = logits.contiguous()
+    if T > 1 and target.stride(1) != 1:
+        target = target.contiguous()
+    ld_l = logits.stride(0) if K > 1 else T
+    ld_t = target.stride(0) if K > 1 else T
+    if ld_l < T or ld_t < T:
+        logits, target, ld_l, ld_t = logits.contiguous(), target.contiguous(), T, T
+    out = torch.empty(K, dtype=torch.float32, device=logits.device)
+    _lib.call("rfd_bce_logits_rowsum", logits.device, K, T, logits.data_ptr(), int(ld_l), target.data_ptr(), int(ld_t),
+              out.data_ptr())
+    return out

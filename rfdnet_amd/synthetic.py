@@ -125,3 +125,22 @@ def synthetic_scene(seed=10, n_raw=120000, n_points=80000, with_origin_pts=True,
     if return_boxes:
         return np.ascontiguousarray(pc[choice]), boxes, np.arange(n_obj, dtype=np.int64) % 8
     return np.ascontiguousarray(pc[choice])
+
+
+def object_occupancy(boxes, n_points=2048, seed=11, fill=0.9):
+    """Per-object completion ground truth for the cuboids `boxes` (G, 7) of synthetic_scene(return_boxes=True), in the
+    layout the reference's test loader gives ISCNet (object_points, object_points_occ, object_voxels):
+    points (G, n_points, 3) float32 uniform in the unit cube [-0.5, 0.5]^3, their occupancies (G, n_points) float32 (1
+    inside) and voxels (G, 16, 16, 16) float32 sampled at the centres of the 16^3 lattice of ONet.compute_loss
+    (-0.5 + 1/32 ... 0.5 - 1/32, x slowest).  The inside of object g is the ellipsoid with semi-axes
+    fill / 2 * size_g / max(size_g): the box's proportions, scaled so that its longest side spans `fill` of the cube."""
+    boxes = np.asarray(boxes, dtype=np.float64)
+    rng = np.random.default_rng(seed)
+    G = boxes.shape[0]
+    axes = 0.5 * fill * boxes[:, 3:6] / boxes[:, 3:6].max(axis=1, keepdims=True)            # (G, 3)
+    pts = rng.random((G, n_points, 3)) - 0.5
+    inside = lambda q: ((q / axes[:, None, :]) ** 2).sum(-1) <= 1.0
+    lin = np.linspace(-0.5 + 1 / 32, 0.5 - 1 / 32, 16)
+    lattice = np.stack(np.meshgrid(lin, lin, lin, indexing='ij'), axis=-1).reshape(1, -1, 3)
+    voxels = inside(np.broadcast_to(lattice, (G, 4096, 3))).reshape(G, 16, 16, 16)
+    return pts.astype(np.float32), inside(pts).astype(np.float32), voxels.astype(np.float32)

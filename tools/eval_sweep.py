@@ -12,6 +12,10 @@ parse_groundtruths reads.  Prints ONE JSON line and writes it to profiles/eval_s
   time between device synchronisations ("scenes_in_flight": 1), the two legs alternating in which goes first.  A
   host-side cost that only shows with several scenes in flight is NOT visible to this tool.
 With seeded weights the mAP is near zero: the tool then exists for the path and the timing ("weights": "seeded").
+--completion (synthetic scenes, one process) adds a leg through ISCNet.evaluate(completion=True) on per-object occupancy
+samples and 16^3 voxels of the ground-truth cuboids (synthetic.object_occupancy): the mean completion loss and voxel IoU
+go into the line as "completion".  It attaches the latent encoder before the weights are seeded, which shifts the
+seeded completion weights: the other figures of such a run are not comparable with a run without the flag.
 With --gpus M the scenes are dealt round robin to M processes (sharding.launch_local_ranks) and the records meet in
 one all_gather (sharding.gather_records); throughput is all scenes over the slowest rank.
 """
@@ -64,6 +68,12 @@ def load_scene(args, i, cfg, files):
                                                    return_boxes=True)
         data = labels_from_boxes(boxes, cls, cfg.dataset_config)
         data['point_clouds'] = pc[None]
+        if getattr(args, 'completion', False):
+            max_obj = data['box_label_mask'].shape[1]
+            for k, a in zip(('object_points', 'object_points_occ', 'object_voxels'),
+                            synthetic.object_occupancy(boxes, seed=args.seed + i)):
+                data[k] = np.zeros((1, max_obj) + a.shape[1:], np.float32)
+                data[k][0, :len(boxes)] = a
     return {k: torch.from_numpy(v).cuda() for k, v in data.items()}
 
 
@@ -79,8 +89,12 @@ def main():
     ap.add_argument("--resolution_0", type=int, default=None)
     ap.add_argument("--upsampling_steps", type=int, default=None)
     ap.add_argument("--no-fit", action="store_true", help="score the decoded boxes without fit_mesh_to_scan")
+    ap.add_argument("--completion", action="store_true",
+                    help="synthetic scenes, --gpus 1: also report the completion loss and the voxel IoU")
     ap.add_argument("--out", type=str, default=os.path.join(ROOT, "profiles", "eval_stage.json"))
     args = ap.parse_args()
+    if args.completion and (args.gt or args.gpus > 1):
+        ap.error("--completion runs on synthetic scenes in one process")
 
     from rfdnet_amd import sharding, synthetic
     if args.gpus > 1 and not sharding.launched():
@@ -97,7 +111,7 @@ def main():
     from rfdnet_amd.iscnet.network import ISCNet
     gen = {k: v for k, v in (('resolution_0', args.resolution_0), ('upsampling_steps', args.upsampling_steps))
            if v is not None}
-    cfg = Config({'generation': gen}, mean_size_arr=args.mean_size_npz)
+    cfg = Config({'generation': gen, 'data': {'latent_encoder': args.completion}}, mean_size_arr=args.mean_size_npz)
     if cfg.dataset_config.placeholder_sizes:
         if args.weight:
             raise FileNotFoundError("a real checkpoint needs the class mean sizes (--mean_size_npz)")
@@ -147,6 +161,15 @@ def main():
         t_on += dt_on
         records.append(rec)
         stage_ms.append(rec.device_ms())
+    completion = None
+    if args.completion:
+        losses, ious = [], []
+        for i in mine:
+            ep = net.evaluate(load_scene(args, i, cfg, files), fit=False, ap_iou_thresh=thr, completion=True)[0]
+            losses.append(float(ep['completion_loss']))
+            ious += [] if ep['iou_stats'] is None else list(ep['iou_stats']['iou'])
+        completion = {"loss": float(np.mean(losses)) if losses else None, "proposals": len(ious),
+                      "voxel_iou": float(np.nanmean(ious)) if ious else None}
     # per rank: scenes, seconds without / with the evaluation, summed stage milliseconds
     mine_t = torch.tensor([len(mine), t_off, t_on, sum(stage_ms)], dtype=torch.float64, device="cuda")
     if dist is not None:
@@ -174,6 +197,8 @@ def main():
                 "eval_stage_device_ms_per_scene": float(times[:, 3].sum() / steps) if steps else None,
                 "compute_metrics_host_s": host_s,
                 "scenes_per_s_without_eval": rate(1), "scenes_per_s_with_eval": rate(2)}
+        if completion is not None:
+            line["completion"] = completion
         text = json.dumps(line)
         print(text)
         if args.out:
