@@ -193,8 +193,7 @@ RFD_API int rfd_box3d_iou(int b, int K, int G, const double *pred_corners, const
                           double *iou3d, double *iou2d, void *stream) {
   if (b <= 0 || K <= 0 || G <= 0) return 0;
   if (b > MAX_SCENES) {                          // b is the grid's y extent
-    rfd_set_error("rfd_box3d_iou: need b <= 65535", hipErrorInvalidValue);
-    return (int)hipErrorInvalidValue;
+    return rfd_invalid("rfd_box3d_iou: need b <= 65535");
   }
   const long pairs = (long)K * G;
   hipLaunchKernelGGL(box3d_iou_kernel, dim3((unsigned)((pairs + IOU_THREADS - 1) / IOU_THREADS), b),
@@ -207,8 +206,7 @@ RFD_API int rfd_ap_match(int b, int C, int K, int G, int nT, const double *iou3d
                          const unsigned char *det_valid, const int *gt_cls, const unsigned char *gt_valid,
                          const double *thr, unsigned char *tp, void *stream) {
   if (K > MATCH_MAX_K || G > MATCH_MAX_G || nT < 1 || nT > MATCH_MAX_T || G < 0 || b > MAX_SCENES || C > MAX_SCENES) {
-    rfd_set_error("rfd_ap_match: need K <= 1024, G <= 256, 1 <= nT <= 4, b and C <= 65535", hipErrorInvalidValue);
-    return (int)hipErrorInvalidValue;
+    return rfd_invalid("rfd_ap_match: need K <= 1024, G <= 256, 1 <= nT <= 4, b and C <= 65535");
   }
   if (b <= 0 || C <= 0 || K <= 0) return 0;
   hipLaunchKernelGGL(ap_match_kernel, dim3(C, b), dim3(MATCH_THREADS), 0, (hipStream_t)stream, C, K, G, nT,

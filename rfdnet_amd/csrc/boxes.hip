@@ -113,7 +113,7 @@ RFD_API int rfd_nms3d(int b, int K, double iou_thr, int old_type, int use_cls, c
                       const int *order, const int *cls, const unsigned char *valid,
                       unsigned char *keep, void *stream) {
   if (b <= 0 || K <= 0) return 0;
-  if (K > 1024) { rfd_set_error("rfd_nms3d: K > 1024", hipErrorInvalidValue); return (int)hipErrorInvalidValue; }
+  if (K > 1024) return rfd_invalid("rfd_nms3d: K > 1024");
   const int threads = ((K + 63) / 64) * 64;
   hipLaunchKernelGGL(nms3d_samecls_kernel, dim3(b), dim3(threads), 0, (hipStream_t)stream, K, iou_thr,
                      old_type, use_cls, aabb, order, cls, valid, keep);

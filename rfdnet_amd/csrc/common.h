@@ -29,6 +29,13 @@ void rfd_set_error(const char *where, hipError_t e);
     }                                          \
   } while (0)
 
+// a launcher's argument check failed: `msg` becomes the last error, the launcher returns hipErrorInvalidValue
+static inline int rfd_invalid(const char *msg) {
+  const hipError_t e = hipErrorInvalidValue;
+  rfd_set_error(msg, e);
+  return (int)e;
+}
+
 // Per-device scratch shared by the persistent kernels (FPS granule exchange,
 // status words, claim counters).  Allocated once per device, never freed.
 constexpr int RFD_ZEROS_FLOATS = 16384;
@@ -65,6 +72,13 @@ struct RfdWorkspace {
   std::atomic<int> fps_test_phantom;  // exchange units that never publish (rfd_fps_test_phantom_units; tests only)
 };
 int rfd_get_workspace(RfdWorkspace **ws);
+// declares `RfdWorkspace *ws` and fetches the device's workspace; the launcher returns the error code on failure
+#define RFD_WORKSPACE(ws)                      \
+  RfdWorkspace *ws;                            \
+  do {                                         \
+    int _rc = rfd_get_workspace(&ws);          \
+    if (_rc) return _rc;                       \
+  } while (0)
 // The status slot (0..RFD_STATUS_SLOTS-1) of `stream`: the slot it already owns, else a free one it claims now,
 // else (null stream, table full) the shared slot 0.  Scenes in flight on different streams must not see (or
 // clear) each other's flags: rfd_stream_status(stream) reads and resets this stream's word only.
@@ -94,6 +108,14 @@ __device__ __forceinline__ float sumsq3(float a, float b, float c) {
   t = __builtin_fmaf(a, a, t);
   t = __builtin_fmaf(c, c, t);
   return t;
+}
+
+// Running float maximum on integer atomics: non-negative floats order like their bit patterns as signed ints, negative
+// ones in reverse as unsigned ints; each atomic is a no-op against a stored value of the other sign (v + 0.f: -0 -> +0).
+// Running max of any sign in a word initialised to -inf, LDS and global memory alike.
+__device__ __forceinline__ void atomic_max_float(float *p, float v) {
+  if (v >= 0.f) atomicMax(reinterpret_cast<int *>(p), __float_as_int(v + 0.f));
+  else atomicMin(reinterpret_cast<unsigned *>(p), __float_as_uint(v));
 }
 
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }

@@ -9,77 +9,23 @@
 //
 // The pooled half of each concatenation is a bias vector per proposal (built in the stage's prologue, f64 sum in a
 // fixed order); a point's input is 16 bytes, so stage s recomputes stages 1 .. s-1 in registers and nothing of width
-// (K, T, *) is ever stored.  As in sa_fused.hip a wave owns 32 points, D[channel, point] = W[channel, k] x[k, point]
-// with the exact-fp32 v_mfma_f32_32x32x2_f32, the accumulator layout of a layer is the B layout of the next one
-// (lane (point, h) holds channels 8q + 4h + e of each 32-channel block) and the 128 x 128 weights are staged per layer
-// in LDS -- two buffers, so the next layer's copy is issued in front of this layer's products.  The 132 KiB of LDS
+// (K, T, *) is ever stored.  The layers are sa_fused.hip's pipeline (f32_wave32.h): a wave owns 32 points, D[channel,
+// point] = W[channel, k] x[k, point] with the exact-fp32 v_mfma_f32_32x32x2_f32, the accumulator layout of a layer is
+// the B layout of the next one and the 128 x 128 weights are staged per layer in LDS -- here in two buffers, so the
+// next layer's copy is issued in front of this layer's products.  The 132 KiB of LDS
 // also keep a CU to one workgroup, i.e. one wave per SIMD: the VALU first layer consumes LDS reads in front of MFMA
 // code, the shape that must not run beside a partner wave's MFMAs (tests/test_isa_audit.py).
 // The max over a proposal's points: lane shuffles, then LDS, then one integer atomic per channel and workgroup on the
-// (K, 128) row (pool_lds's sign-aware idiom, pointseg_chain.hip) -- exact, hence independent of order and grid.
-#include "common.h"
+// (K, 128) row (atomic_max_float, common.h) -- exact, hence independent of order and grid.
+#include "f32_wave32.h"
 #include "../../include/rfd_latent.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using namespace f32_wave32;
 
 constexpr int LH = 128;                    // hidden width
 constexpr int LW = LH * LH;                // floats of one packed layer (64 KiB)
-
-__device__ __forceinline__ f32x16 mfma32(float a, float b, f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
-}
-
-// running max of any sign in a word initialised to -inf: LDS and global memory alike
-__device__ __forceinline__ void pool_max(float *p, float v) {
-  if (v >= 0.f) atomicMax(reinterpret_cast<int *>(p), __float_as_int(v + 0.f));
-  else atomicMin(reinterpret_cast<unsigned *>(p), __float_as_uint(v));
-}
-
-// acc[b] = sum_j W[32b.., position 2j + h] * bin[j]; packed W in LDS as [block b][j4][lane][4 floats]
-__device__ __forceinline__ void layer(const float *s_w, const float (&bin)[LH / 2], f32x16 (&acc)[4], int lane) {
-#pragma unroll
-  for (int b = 0; b < 4; ++b) acc[b] = f32x16{0.f};
-  const f32x4 *w = reinterpret_cast<const f32x4 *>(s_w) + lane;
-#pragma unroll
-  for (int j4 = 0; j4 < LH / 8; ++j4) {
-#pragma unroll
-    for (int b = 0; b < 4; ++b) {
-      const f32x4 w4 = w[(b * (LH / 8) + j4) * 64];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) acc[b] = mfma32(w4[e], bin[4 * j4 + e], acc[b]);
-    }
-  }
-}
-
-// + bias in place (natural channel order in LDS)
-__device__ __forceinline__ void add_bias(f32x16 (&acc)[4], const float *s_bias, int half) {
-#pragma unroll
-  for (int b = 0; b < 4; ++b)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const f32x4 bv = *reinterpret_cast<const f32x4 *>(s_bias + 32 * b + 8 * q + 4 * half);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) acc[b][4 * q + e] = acc[b][4 * q + e] + bv[e];
-    }
-}
-
-// the next layer's B operand: relu of the accumulators, register r of block b = k-step 16b + r
-__device__ __forceinline__ void relu_to_b(const f32x16 (&acc)[4], float (&bin)[LH / 2]) {
-#pragma unroll
-  for (int j = 0; j < LH / 2; ++j) {
-    const float v = acc[j >> 4][j & 15];
-    bin[j] = v > 0.f ? v : 0.f;
-  }
-}
-
-__device__ __forceinline__ void stage_w(float *s_w, const float *__restrict__ g_w, int t) {
-  const f32x4 *src = reinterpret_cast<const f32x4 *>(g_w);
-  f32x4 *dst = reinterpret_cast<f32x4 *>(s_w);
-  for (int i = t; i < LW / 4; i += 256) dst[i] = src[i];
-}
 
 // s_bias[c] = b[c] + sum_k wT[k][c] relu(pooled[k]): two halves of k in f64, added in a fixed order, rounded once.
 // All 256 threads call it; s_m / s_part are scratch; ends with a barrier.
@@ -118,8 +64,8 @@ __global__ __launch_bounds__(256) void latent_stage_kernel(
   const int row = (tile * 4 + wave) * 32 + nrow;            // may run past the end
   const bool live = row < T;
 
-  stage_w(s_w[0], wa, t);
-  if (STAGE >= 2) stage_w(s_w[1], wa + LW, t);
+  stage(s_w[0], wa, LW, t);
+  if (STAGE >= 2) stage(s_w[1], wa + LW, LW, t);
   if (t < LH) {
     s_l0[t] = reinterpret_cast<const f32x4 *>(l0)[t];
     s_b0[t] = bias0[(size_t)k * LH + t];
@@ -146,20 +92,20 @@ __global__ __launch_bounds__(256) void latent_stage_kernel(
     }
   }
   f32x16 acc[4];
-  layer(s_w[0], bin, acc, lane);
-  add_bias(acc, s_bias[0], half);
+  layer<LH / 2, 4>(s_w[0], bin, acc, lane);
+  add_bias<false>(acc, s_bias[0], half);
   if (STAGE >= 2) {
     __syncthreads();                                      // every wave is done with buffer 0
-    if (STAGE >= 3) stage_w(s_w[0], wa + 2 * LW, t);
-    relu_to_b(acc, bin);
-    layer(s_w[1], bin, acc, lane);
-    add_bias(acc, s_bias[1], half);
+    if (STAGE >= 3) stage(s_w[0], wa + 2 * LW, LW, t);
+    acc_to_b<true>(acc, bin);
+    layer<LH / 2, 4>(s_w[1], bin, acc, lane);
+    add_bias<false>(acc, s_bias[1], half);
   }
   if (STAGE >= 3) {
     __syncthreads();                                      // fc_3's fragments have landed
-    relu_to_b(acc, bin);
-    layer(s_w[0], bin, acc, lane);
-    add_bias(acc, s_bias[2], half);
+    acc_to_b<true>(acc, bin);
+    layer<LH / 2, 4>(s_w[0], bin, acc, lane);
+    add_bias<false>(acc, s_bias[2], half);
   }
 
   // ---- max over the live points: the 32 lanes of a half, then LDS, then the proposal's row
@@ -175,10 +121,10 @@ __global__ __launch_bounds__(256) void latent_stage_kernel(
 #pragma unroll
     for (int b = 0; b < 4; ++b)
 #pragma unroll
-      for (int r = 0; r < 16; ++r) pool_max(s_pool + 32 * b + 8 * (r >> 2) + 4 * half + (r & 3), acc[b][r]);
+      for (int r = 0; r < 16; ++r) atomic_max_float(s_pool + 32 * b + 8 * (r >> 2) + 4 * half + (r & 3), acc[b][r]);
   }
   __syncthreads();
-  if (t < LH) pool_max(pool + ((size_t)(STAGE - 1) * K + k) * LH + t, s_pool[t]);
+  if (t < LH) atomic_max_float(pool + ((size_t)(STAGE - 1) * K + k) * LH + t, s_pool[t]);
 }
 
 // bias0[k] = b0 + c[k] . wcT (two halves of c_dim in f64, fixed order); pool = -inf.  One workgroup per proposal.
@@ -289,17 +235,12 @@ __global__ __launch_bounds__(256) void voxel_iou_kernel(int V, const float *__re
   }
 }
 
-int bad(const char *what) {
-  rfd_set_error(what, hipErrorInvalidValue);
-  return (int)hipErrorInvalidValue;
-}
-
 }  // namespace
 
 RFD_API int rfd_latent_prep(int K, int c_dim, const float *c, const float *wcT, const float *b0, float *bias0,
                             float *pool, void *stream) {
   if (K <= 0) return 0;
-  if (c_dim < 0 || (c_dim > 0 && (c == nullptr || wcT == nullptr))) return bad("rfd_latent_prep: c_dim / c / wcT");
+  if (c_dim < 0 || (c_dim > 0 && (c == nullptr || wcT == nullptr))) return rfd_invalid("rfd_latent_prep: c_dim / c / wcT");
   hipLaunchKernelGGL(latent_prep_kernel, dim3(K), dim3(256), 0, (hipStream_t)stream, K, c_dim, c, wcT, b0, bias0, pool);
   RFD_CHECK_LAUNCH();
   return 0;
@@ -309,10 +250,10 @@ RFD_API int rfd_latent_stage(int stage, int K, int T, const float *p, const floa
                              const float *bias0, const float *wa, const float *wbT, const float *b123, float *pool,
                              void *stream) {
   if (K <= 0) return 0;
-  if (T <= 0) return bad("rfd_latent_stage: T >= 1 (the max over no points is undefined)");
+  if (T <= 0) return rfd_invalid("rfd_latent_stage: T >= 1 (the max over no points is undefined)");
   const int tiles = (T + 127) / 128;
-  if ((long long)tiles * K > 0x7fffffffLL) return bad("rfd_latent_stage: K * ceil(T / 128) must fit in 31 bits");
-  if (((uintptr_t)l0 & 15) || ((uintptr_t)wa & 15)) return bad("rfd_latent_stage: 16-byte aligned l0 / wa");
+  if ((long long)tiles * K > 0x7fffffffLL) return rfd_invalid("rfd_latent_stage: K * ceil(T / 128) must fit in 31 bits");
+  if (((uintptr_t)l0 & 15) || ((uintptr_t)wa & 15)) return rfd_invalid("rfd_latent_stage: 16-byte aligned l0 / wa");
   const dim3 grid((unsigned)(tiles * K));
   hipStream_t s = (hipStream_t)stream;
 #define RFD_LATENT_CASE(S)                                                                                        \
@@ -326,14 +267,14 @@ RFD_API int rfd_latent_stage(int stage, int K, int T, const float *p, const floa
   RFD_LATENT_CASE(2)
   RFD_LATENT_CASE(3)
 #undef RFD_LATENT_CASE
-  return bad("rfd_latent_stage: stage must be 1, 2 or 3");
+  return rfd_invalid("rfd_latent_stage: stage must be 1, 2 or 3");
 }
 
 RFD_API int rfd_latent_head(int K, int z_dim, const float *pool3, const float *whT, const float *bh, const float *eps,
                             float *mean, float *logstd, float *z, float *kl, void *stream) {
   if (K <= 0) return 0;
-  if (z_dim < 1 || z_dim > 512) return bad("rfd_latent_head: 1 <= z_dim <= 512");
-  if (z != nullptr && eps == nullptr) return bad("rfd_latent_head: z needs eps");
+  if (z_dim < 1 || z_dim > 512) return rfd_invalid("rfd_latent_head: 1 <= z_dim <= 512");
+  if (z != nullptr && eps == nullptr) return rfd_invalid("rfd_latent_head: z needs eps");
   hipLaunchKernelGGL(latent_head_kernel, dim3(K), dim3(256), 0, (hipStream_t)stream, z_dim, pool3, whT, bh, eps, mean,
                      logstd, z, kl);
   RFD_CHECK_LAUNCH();
@@ -343,7 +284,7 @@ RFD_API int rfd_latent_head(int K, int z_dim, const float *pool3, const float *w
 RFD_API int rfd_bce_logits_rowsum(int K, int T, const float *logits, int ld_logits, const float *target, int ld_target,
                                   float *out, void *stream) {
   if (K <= 0) return 0;
-  if (T < 0 || ld_logits < T || ld_target < T) return bad("rfd_bce_logits_rowsum: row strides must cover T");
+  if (T < 0 || ld_logits < T || ld_target < T) return rfd_invalid("rfd_bce_logits_rowsum: row strides must cover T");
   hipLaunchKernelGGL(bce_rowsum_kernel, dim3(K), dim3(256), 0, (hipStream_t)stream, T, logits, ld_logits, target,
                      ld_target, out);
   RFD_CHECK_LAUNCH();
@@ -353,7 +294,7 @@ RFD_API int rfd_bce_logits_rowsum(int K, int T, const float *logits, int ld_logi
 RFD_API int rfd_voxel_iou(int K, int V, const float *logits, int ld_logits, float logit_threshold, const float *gt,
                           int *inter, int *uni, void *stream) {
   if (K <= 0) return 0;
-  if (V < 0 || ld_logits < V) return bad("rfd_voxel_iou: the row stride must cover V");
+  if (V < 0 || ld_logits < V) return rfd_invalid("rfd_voxel_iou: the row stride must cover V");
   hipLaunchKernelGGL(voxel_iou_kernel, dim3(K), dim3(256), 0, (hipStream_t)stream, V, logits, ld_logits,
                      logit_threshold, gt, inter, uni);
   RFD_CHECK_LAUNCH();

@@ -255,9 +255,9 @@ __device__ __forceinline__ float dpp_max(float v) {
 // otherwise every wave finishes its own columns.  The atomics cross the XCDs' private L2s and
 // were the limit of these launches (8.4 M per K = 128 layer), not the arithmetic.
 // max commutes with the monotone fma / ReLU, so the result is bit-identical to rows_epilogue's.
-// Running float maximum on integer atomics: non-negative floats order like their bit patterns as signed ints, negative
-// ones in reverse as unsigned ints; each atomic is a no-op against a stored value of the other sign.  !is_signed: the
-// pool holds max(0, .) (zero-initialised; every consumer rectifies the pooled vector), so v <= 0 changes nothing.
+// The signed branch is atomic_max_float (common.h, where the integer-atomic idiom is explained); it keeps its own text because
+// on the shared definition the row-owner kernels get another register allocation (their instruction streams are frozen).
+// !is_signed: the pool holds max(0, .) (zero-initialised; every consumer rectifies the pooled vector), so v <= 0 changes nothing.
 __device__ __forceinline__ void pool_atomic(int *p, float v, int is_signed) {
   if (v > 0.f) atomicMax(p, __float_as_int(v));
   else if (is_signed) {
@@ -932,7 +932,7 @@ static int launch_pack(int N, int K, int sw, const float *W, void *packed, void 
 
 // W [N][K] fp32 (device) -> packed (device).  N % 128 == 0, K % 32 == 0.
 RFD_API int rfd_gemm_pack_w(int N, int K, int sw, const float *W, void *packed, void *stream) {
-  if (N % BN || K % BK) { rfd_set_error("rfd_gemm_pack_w: N % 128 or K % 32", hipErrorInvalidValue); return (int)hipErrorInvalidValue; }
+  if (N % BN || K % BK) return rfd_invalid("rfd_gemm_pack_w: N % 128 or K % 32");
   if (int rc = launch_pack<PACK_TILE>(N, K, sw, W, packed, stream)) return rc;
   if (N % RN == 0 && K % 128 == 0) {                 // the shapes the row-owner kernels take
     if (int rc = launch_pack<PACK_ROWS>(N, K, sw, W, packed, stream)) return rc;
@@ -949,13 +949,9 @@ RFD_API int rfd_gemm_f16x3(int M, int N, int K, const float *A, int lda, const v
                            int rows_per_group, const float *R, int ldr, int relu_in, int relu_out,
                            int sa, int sw, float *pool_max, int pool_signed, void *stream) {
   if (M <= 0) return 0;
-  if (!C && !pool_max) {
-    rfd_set_error("rfd_gemm_f16x3: C == NULL without pool_max", hipErrorInvalidValue);
-    return (int)hipErrorInvalidValue;
-  }
+  if (!C && !pool_max) return rfd_invalid("rfd_gemm_f16x3: C == NULL without pool_max");
   if (M % BM || N % BN || K % BK || (lda & 3)) {
-    rfd_set_error("rfd_gemm_f16x3: shape not a multiple of the 128x128x32 tile", hipErrorInvalidValue);
-    return (int)hipErrorInvalidValue;
+    return rfd_invalid("rfd_gemm_f16x3: shape not a multiple of the 128x128x32 tile");
   }
   Args g;
   g.A = A; g.lda = lda; g.Wp = (const half8 *)packed_w; g.C = C; g.ldc = ldc; g.bias = bias;
@@ -965,8 +961,7 @@ RFD_API int rfd_gemm_f16x3(int M, int N, int K, const float *A, int lda, const v
   g.pool = pool_max;
   g.pool_signed = pool_signed;
   g.gbias_stride = N;
-  RfdWorkspace *ws;
-  if (int rc = rfd_get_workspace(&ws)) return rc;
+  RFD_WORKSPACE(ws);
   g.status = rfd_status_word(ws, (hipStream_t)stream);
   // RFD_GEMM_TILE_ONLY: A/B switch of tools/gemm_bench.py (the tile kernel for every shape), read once per process
   static const bool tile_only = getenv("RFD_GEMM_TILE_ONLY") != nullptr;
@@ -987,9 +982,8 @@ RFD_API int rfd_gemm_f16x3(int M, int N, int K, const float *A, int lda, const v
     else hipLaunchKernelGGL((gemm_rows8_kernel<false, false>), grid, dim3(512), 0, s, g);
   } else {
     if (pool_max || !C) {
-      rfd_set_error("rfd_gemm_f16x3: pool_max / C == NULL need the row-owner kernel (M, N % 256, K % 128, "
-                    "rows_per_group % 64, 16-byte aligned operands)", hipErrorInvalidValue);
-      return (int)hipErrorInvalidValue;
+      return rfd_invalid("rfd_gemm_f16x3: pool_max / C == NULL need the row-owner kernel (M, N % 256, K % 128, "
+                         "rows_per_group % 64, 16-byte aligned operands)");
     }
     hipLaunchKernelGGL(gemm_f16x3_kernel, dim3((M / BM) * (N / BN)), dim3(256), 0, (hipStream_t)stream, g);
   }
@@ -1005,12 +999,9 @@ RFD_API int rfd_rows_to_frag(int M, int C, const float *x, int ldx, int relu, in
                              void *stream) {
   if (M <= 0 || C <= 0) return 0;
   if (M % 32 || C % 32 || (ldx & 3) || ((uintptr_t)x & 15) || ((uintptr_t)out & 15) || (rb_stride & 15)) {
-    rfd_set_error("rfd_rows_to_frag: M % 32, C % 32, 16-byte aligned rows / blocks", hipErrorInvalidValue);
-    return (int)hipErrorInvalidValue;
+    return rfd_invalid("rfd_rows_to_frag: M % 32, C % 32, 16-byte aligned rows / blocks");
   }
-  RfdWorkspace *ws;
-  int rc = rfd_get_workspace(&ws);
-  if (rc) return rc;
+  RFD_WORKSPACE(ws);
   const size_t units = (size_t)(M / 32) * (C / 32);
   hipLaunchKernelGGL(rows_to_frag_kernel, dim3((unsigned)((units + 3) / 4)), dim3(256), 0, (hipStream_t)stream, M, C, x,
                      ldx, relu, ldexpf(1.f, sa), (unsigned char *)out, rb_stride, rfd_status_word(ws, (hipStream_t)stream));
@@ -1021,8 +1012,7 @@ RFD_API int rfd_rows_to_frag(int M, int C, const float *x, int ldx, int relu, in
 RFD_API int rfd_frag_to_rows(int M, int C, const void *in, long rb_stride, int sa, float *x, int ldx, void *stream) {
   if (M <= 0 || C <= 0) return 0;
   if (M % 32 || C % 32 || (ldx & 3) || ((uintptr_t)x & 15) || ((uintptr_t)in & 15) || (rb_stride & 15)) {
-    rfd_set_error("rfd_frag_to_rows: M % 32, C % 32, 16-byte aligned rows / blocks", hipErrorInvalidValue);
-    return (int)hipErrorInvalidValue;
+    return rfd_invalid("rfd_frag_to_rows: M % 32, C % 32, 16-byte aligned rows / blocks");
   }
   const size_t units = (size_t)(M / 32) * (C / 32);
   hipLaunchKernelGGL(frag_to_rows_kernel, dim3((unsigned)((units + 3) / 4)), dim3(256), 0, (hipStream_t)stream, M, C,
@@ -1041,21 +1031,15 @@ RFD_API int rfd_gemm_f16x3_frag(int M, int N, int K, const void *A_frag, long a_
                                 int gbias_stride, int rows_per_group, int sa, int sw, float *pool_max, int pool_signed,
                                 void *stream) {
   if (M <= 0) return 0;
-  if (!C_frag && !pool_max) {
-    rfd_set_error("rfd_gemm_f16x3_frag: C_frag == NULL without pool_max", hipErrorInvalidValue);
-    return (int)hipErrorInvalidValue;
-  }
+  if (!C_frag && !pool_max) return rfd_invalid("rfd_gemm_f16x3_frag: C_frag == NULL without pool_max");
   const int rpg = rows_per_group > 0 ? rows_per_group : 1;
   if (M % RM || N % RN || K % 128 || N > RFD_ZEROS_FLOATS || ((gbias || pool_max) && rpg % 64) || (a_rb_stride & 15) ||
       (c_rb_stride & 15) || ((uintptr_t)A_frag & 15) || ((uintptr_t)C_frag & 15) || ((uintptr_t)bias & 15) ||
       ((uintptr_t)gbias & 15) || (gbias_stride & 3)) {
-    rfd_set_error("rfd_gemm_f16x3_frag: need M % 256, N % 256, K % 128, rows_per_group % 64, 16-byte aligned operands",
-                  hipErrorInvalidValue);
-    return (int)hipErrorInvalidValue;
+    return rfd_invalid("rfd_gemm_f16x3_frag: need M % 256, N % 256, K % 128, rows_per_group % 64, "
+                       "16-byte aligned operands");
   }
-  RfdWorkspace *ws;
-  int rc = rfd_get_workspace(&ws);
-  if (rc) return rc;
+  RFD_WORKSPACE(ws);
   Args g;
   g.A = nullptr; g.lda = 0; g.Wp = (const half8 *)packed_w; g.C = nullptr; g.ldc = 0;
   g.bias = bias ? bias : ws->zeros;

@@ -171,10 +171,7 @@ RFD_API int three_interpolate_grad_kernel_wrapper(int b, int c, int n, int m,
 RFD_API int rfd_three_interpolate_cat(int b, int c, int cs, int m, int n, const float *points, const int *idx,
                                       const float *dist2, const float *skip, float *out, void *stream) {
   if (b <= 0 || c + cs <= 0 || n <= 0) return 0;
-  if (c < 0 || cs < 0 || (cs > 0 && !skip)) {
-    rfd_set_error("rfd_three_interpolate_cat: channel counts / skip", hipErrorInvalidValue);
-    return (int)hipErrorInvalidValue;
-  }
+  if (c < 0 || cs < 0 || (cs > 0 && !skip)) return rfd_invalid("rfd_three_interpolate_cat: channel counts / skip");
   hipLaunchKernelGGL(three_interpolate_cat_kernel, dim3(ceil_div(n, 256), c + cs, b), dim3(256), 0,
                      (hipStream_t)stream, c, cs, m, n, points, idx, dist2, skip, out);
   RFD_CHECK_LAUNCH();

@@ -209,17 +209,12 @@ __global__ __launch_bounds__(256) void refine_dirichlet_kernel(int n, unsigned l
   st3(out, i, e);
 }
 
-int bad_args(const char *what) {
-  rfd_set_error(what, hipErrorInvalidValue);
-  return (int)hipErrorInvalidValue;
-}
-
 }  // namespace
 
 RFD_API int rfd_refine_sample(int F, int K, const float *verts, const int *faces, const int *fend, const int *vend,
                               const int *tprefix, const float *eps, double *qd, float *qt, void *stream) {
   if (F < 0 || K <= 0 || !verts || !faces || !fend || !vend || !tprefix || !eps || !qd || !qt)
-    return bad_args("rfd_refine_sample: arguments");
+    return rfd_invalid("rfd_refine_sample: arguments");
   if (F == 0) return 0;
   hipLaunchKernelGGL(refine_sample_kernel, dim3(ceil_div(F, 256)), dim3(256), 0, (hipStream_t)stream, F, K, verts, faces,
                      fend, vend, tprefix, eps, qd, qt);
@@ -231,7 +226,7 @@ RFD_API int rfd_refine_face_backward(int F, int K, const float *verts, const int
                                      const int *tprefix, const float *eps, const float *logits, const float *grad,
                                      float tau, double *cg, void *stream) {
   if (F < 0 || K <= 0 || !verts || !faces || !fend || !vend || !tprefix || !eps || !logits || !grad || !cg)
-    return bad_args("rfd_refine_face_backward: arguments");
+    return rfd_invalid("rfd_refine_face_backward: arguments");
   if (F == 0) return 0;
   hipLaunchKernelGGL(refine_face_backward_kernel, dim3(ceil_div(F, 256)), dim3(256), 0, (hipStream_t)stream, F, K, verts,
                      faces, fend, vend, tprefix, eps, logits, grad, tau, cg);
@@ -242,7 +237,7 @@ RFD_API int rfd_refine_face_backward(int F, int K, const float *verts, const int
 RFD_API int rfd_refine_vertex_step(int V, const int *rowptr, const int *col, int n_corners, const double *cg, float *verts,
                                    float *sq, float *gout, void *stream) {
   if (V < 0 || n_corners < 0 || !rowptr || !col || !cg || !verts || !sq)
-    return bad_args("rfd_refine_vertex_step: arguments");
+    return rfd_invalid("rfd_refine_vertex_step: arguments");
   if (V == 0) return 0;
   hipLaunchKernelGGL(refine_vertex_step_kernel, dim3(ceil_div(V, 256)), dim3(256), 0, (hipStream_t)stream, V, rowptr, col,
                      n_corners, cg, verts, sq, gout);
@@ -251,7 +246,7 @@ RFD_API int rfd_refine_vertex_step(int V, const int *rowptr, const int *col, int
 }
 
 RFD_API int rfd_refine_dirichlet(int n, unsigned long long seed, int step, float *out, void *stream) {
-  if (n < 0 || step < 0 || !out) return bad_args("rfd_refine_dirichlet: arguments");
+  if (n < 0 || step < 0 || !out) return rfd_invalid("rfd_refine_dirichlet: arguments");
   if (n == 0) return 0;
   hipLaunchKernelGGL(refine_dirichlet_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, (hipStream_t)stream, n, seed, step, out);
   RFD_CHECK_LAUNCH();

@@ -725,8 +725,7 @@ RFD_API int rfd_mise_subdivide_dirty(int K, int res0, int depth, double threshol
                                      unsigned char *dirty_next, int use_dirty, void *stream) {
   if (K <= 0 || depth <= 0) return 0;
   if (!dirty_cur || !dirty_next || (use_dirty && (!lin || !tile_prop || n_slots < 0))) {
-    rfd_set_error("rfd_mise_subdivide_dirty: dirty maps / query list", hipErrorInvalidValue);
-    return (int)hipErrorInvalidValue;
+    return rfd_invalid("rfd_mise_subdivide_dirty: dirty maps / query list");
   }
   const int R1 = (res0 << depth) + 1;
   const size_t d_per = dirty_offset(res0, depth);

@@ -127,16 +127,12 @@ RFD_API int rfd_mlp_cols(int B, int N, int n_layers, const int *widths, const fl
                          const int *relu, const float *x, float *y, void *stream) {
   if (B <= 0 || N <= 0) return 0;
   if (n_layers < 1 || n_layers > 4 || (N % MLP_P) || ((uintptr_t)x & 15) || ((uintptr_t)y & 15)) {
-    rfd_set_error("rfd_mlp_cols: 1 .. 4 layers, N % 8 == 0, 16-byte aligned x / y", hipErrorInvalidValue);
-    return (int)hipErrorInvalidValue;
+    return rfd_invalid("rfd_mlp_cols: 1 .. 4 layers, N % 8 == 0, 16-byte aligned x / y");
   }
   MlpArgs a;
   a.n_layers = n_layers; a.N = N; a.x = x; a.y = y;
   for (int i = 0; i <= n_layers; ++i) {
-    if (widths[i] < 1 || widths[i] > MLP_CMAX) {
-      rfd_set_error("rfd_mlp_cols: layer width outside 1 .. 1024", hipErrorInvalidValue);
-      return (int)hipErrorInvalidValue;
-    }
+    if (widths[i] < 1 || widths[i] > MLP_CMAX) return rfd_invalid("rfd_mlp_cols: layer width outside 1 .. 1024");
     a.width[i] = widths[i];
   }
   for (int i = 0; i < 4; ++i) {
@@ -144,8 +140,7 @@ RFD_API int rfd_mlp_cols(int B, int N, int n_layers, const int *widths, const fl
     a.bias[i] = i < n_layers ? bias[i] : nullptr;
     a.relu[i] = i < n_layers ? relu[i] : 0;
     if (i < n_layers && ((uintptr_t)wt[i] & 15)) {
-      rfd_set_error("rfd_mlp_cols: transposed weights must be 16-byte aligned", hipErrorInvalidValue);
-      return (int)hipErrorInvalidValue;
+      return rfd_invalid("rfd_mlp_cols: transposed weights must be 16-byte aligned");
     }
   }
   hipLaunchKernelGGL(mlp_cols_kernel, dim3(N / MLP_P, B), dim3(MLP_THREADS), 0, (hipStream_t)stream, a);

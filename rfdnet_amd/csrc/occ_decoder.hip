@@ -435,9 +435,7 @@ RFD_API int rfd_occ_decode(int n_tiles, const float *pts, const int *tile_prop,
                            float fc_out_b, float *logits, int mode,
                            void *stream) {
   if (n_tiles <= 0) return 0;
-  RfdWorkspace *ws;
-  int rc = rfd_get_workspace(&ws);
-  if (rc) return rc;
+  RFD_WORKSPACE(ws);
   hipStream_t s = (hipStream_t)stream;
   // one persistent workgroup per CU (the kernel owns the CU: 158 KiB LDS, 1 wave/SIMD)
   const int ncu = ws->num_cu > 0 ? ws->num_cu : 256;
@@ -452,8 +450,7 @@ RFD_API int rfd_occ_decode(int n_tiles, const float *pts, const int *tile_prop,
                        tile_prop, tile_src, (const half8 *)packed, fc_p_w, table, fc_out_w, fc_out_b,
                        logits, rfd_status_word(ws, s), tiles_per_wg);
   } else {
-    rfd_set_error("rfd_occ_decode: unknown mode", hipErrorInvalidValue);
-    return (int)hipErrorInvalidValue;
+    return rfd_invalid("rfd_occ_decode: unknown mode");
   }
   RFD_CHECK_LAUNCH();
   return 0;

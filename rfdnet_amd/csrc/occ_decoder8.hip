@@ -572,9 +572,7 @@ static int decode_w8(int n_tiles, const float *pts, const int *tile_prop, const 
                      float fc_out_b, float *logits, const int *lin, float *values, unsigned char *pstate,
                      size_t n_per, int mode, void *stream) {
   if (n_tiles <= 0) return 0;
-  RfdWorkspace *ws;
-  int rc = rfd_get_workspace(&ws);
-  if (rc) return rc;
+  RFD_WORKSPACE(ws);
   hipStream_t s = (hipStream_t)stream;
   int ncu = ws->num_cu > 0 ? ws->num_cu : 256;
   const LaunchShape &ls = launch_shape();
@@ -604,8 +602,7 @@ static int decode_w8(int n_tiles, const float *pts, const int *tile_prop, const 
                        (const half8 *)packed, fc_p_w, table, fc_out_w, fc_out_b, logits, rfd_status_word(ws, s), tiles_per_wg,
                        lin, values, pstate, n_per, claim);
   } else {
-    rfd_set_error("rfd_occ_decode_w8: unknown mode", hipErrorInvalidValue);
-    return (int)hipErrorInvalidValue;
+    return rfd_invalid("rfd_occ_decode_w8: unknown mode");
   }
   RFD_CHECK_LAUNCH();
   return 0;
@@ -625,8 +622,7 @@ RFD_API int rfd_occ_decode_scatter_w8(int n_tiles, const float *pts, const int *
                                       const float *fc_out_w, float fc_out_b, const int *lin, float *values,
                                       unsigned char *pstate, long long n_per, int mode, void *stream) {
   if (!lin || !values || !pstate || n_per <= 0) {
-    rfd_set_error("rfd_occ_decode_scatter_w8: lin / values / pstate / n_per", hipErrorInvalidValue);
-    return (int)hipErrorInvalidValue;
+    return rfd_invalid("rfd_occ_decode_scatter_w8: lin / values / pstate / n_per");
   }
   return decode_w8(n_tiles, pts, tile_prop, tile_src, packed, fc_p_w, table, fc_out_w, fc_out_b, nullptr, lin,
                    values, pstate, (size_t)n_per, mode, stream);

@@ -195,8 +195,7 @@ int rfd_occ_tail_launch(int n_tiles, const float *pts, const int *tile_prop, con
     hipLaunchKernelGGL(occ_decode_tail_kernel<1>, grid, block, 0, stream, pts, tile_prop, tile_src, (const half8 *)packed,
                        fc_p_w, table, fc_out_w, fc_out_b, logits, status, lin, values, pstate, n_per, n_tiles);
   } else {
-    rfd_set_error("rfd_occ_decode_w8: unknown mode", hipErrorInvalidValue);
-    return (int)hipErrorInvalidValue;
+    return rfd_invalid("rfd_occ_decode_w8: unknown mode");
   }
   RFD_CHECK_LAUNCH();
   return 0;

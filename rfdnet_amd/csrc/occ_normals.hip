@@ -360,18 +360,12 @@ RFD_API int rfd_occ_normals_w8(int n_groups, const double *verts, const int *ven
                                const void *packed_fwd, const void *packed_bwd, const int *kw, const float *fc_p_w,
                                const float *table, const float *fc_out_w, float *normals, float *grad, int mode,
                                void *stream) {
-  if (mode != RFD_OCC_MODE_F16X3) {
-    rfd_set_error("rfd_occ_normals_w8: only RFD_OCC_MODE_F16X3 is supported", hipErrorInvalidValue);
-    return (int)hipErrorInvalidValue;
-  }
+  if (mode != RFD_OCC_MODE_F16X3) return rfd_invalid("rfd_occ_normals_w8: only RFD_OCC_MODE_F16X3 is supported");
   if (n_groups < 0 || K <= 0 || !kw || !verts || !vend || !gprefix || !normals) {
-    rfd_set_error("rfd_occ_normals_w8: arguments", hipErrorInvalidValue);
-    return (int)hipErrorInvalidValue;
+    return rfd_invalid("rfd_occ_normals_w8: arguments");
   }
   if (n_groups == 0) return 0;
-  RfdWorkspace *ws;
-  int rc = rfd_get_workspace(&ws);
-  if (rc) return rc;
+  RFD_WORKSPACE(ws);
   hipStream_t s = (hipStream_t)stream;
   Exps ex;
   for (int j = 0; j < NB; ++j) {

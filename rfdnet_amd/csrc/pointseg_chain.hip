@@ -95,11 +95,6 @@ struct ChainArgs {
   unsigned *status;
 };
 
-__device__ __forceinline__ void pool_lds(float *p, float v) {          // running max in LDS, any sign (initialised to -inf)
-  if (v >= 0.f) atomicMax(reinterpret_cast<int *>(p), __float_as_int(v + 0.f));
-  else atomicMin(reinterpret_cast<unsigned *>(p), __float_as_uint(v));
-}
-
 template <int MODE>
 __global__ __launch_bounds__(512) void chain_kernel(ChainArgs a) {
   __shared__ __attribute__((aligned(16))) unsigned char smem[SMEM];
@@ -275,7 +270,7 @@ __global__ __launch_bounds__(512) void chain_kernel(ChainArgs a) {
         m = o > m ? o : m;
         o = __shfl_xor(m, 32);
         m = o > m ? o : m;
-        if (lane < 16) pool_lds(s_red + 16 * (4 * i + tt) + n, m);
+        if (lane < 16) atomic_max_float(s_red + 16 * (4 * i + tt) + n, m);
         asm volatile("" ::"v"(cw[0]), "v"(cw[1]), "v"(cw[2]), "v"(cw[3]), "v"(cw[4]), "v"(cw[5]), "v"(cw[6]), "v"(cw[7]));
         if (tt < 3) {
 #pragma unroll
@@ -533,8 +528,7 @@ RFD_API size_t rfd_chain_packed_bytes_n(int c3) {
 RFD_API int rfd_chain_pack_n(int mode, int c3, const float *W1, const float *W2, const float *W3, int sw1, int sw2,
                              int sw3, void *packed, void *stream) {
   if (mode < 0 || mode > 2 || !W2 || !W3 || (mode == 2 && !W1) || !chain_width_ok(c3)) {
-    rfd_set_error("rfd_chain_pack_n: mode / weights / width (64 .. 1024, multiple of 64)", hipErrorInvalidValue);
-    return (int)hipErrorInvalidValue;
+    return rfd_invalid("rfd_chain_pack_n: mode / weights / width (64 .. 1024, multiple of 64)");
   }
   const size_t total = rfd_chain_packed_bytes_n(c3) / 2;
   hipLaunchKernelGGL(chain_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, mode,
@@ -552,15 +546,10 @@ RFD_API int rfd_chain_pool_n(int mode, int c3, int M, int P, int d_in, const flo
   if (mode < 0 || mode > 2 || P <= 0 || P % 512 || M % P || (mode == 1 && (d_in < 1 || d_in > 8 || !W1raw)) ||
       (mode != 1 && (d_in != 64 || (ldx & 3) || ((uintptr_t)x & 15))) || (mode && !b1) || !b2 || !b3 || !out ||
       !chain_width_ok(c3)) {
-    rfd_set_error("rfd_chain_pool_n: need P % 512 == 0, M % P == 0, d_in <= 8 (mode 1) or 64 with 16-byte rows, "
-                  "last width 64 .. 1024 in steps of 64", hipErrorInvalidValue);
-    return (int)hipErrorInvalidValue;
+    return rfd_invalid("rfd_chain_pool_n: need P % 512 == 0, M % P == 0, d_in <= 8 (mode 1) or 64 with 16-byte rows, "
+                       "last width 64 .. 1024 in steps of 64");
   }
-  RfdWorkspace *ws;
-  {
-    int rc = rfd_get_workspace(&ws);
-    if (rc) return rc;
-  }
+  RFD_WORKSPACE(ws);
   ChainArgs a;
   a.M = M; a.P = P; a.d_in = d_in; a.ldx = ldx; a.relu3 = relu3; a.c3 = c3; a.x = x; a.packed = (const half8 *)packed;
   a.W1raw = W1raw; a.b1 = b1; a.b2 = b2; a.b3 = b3;
@@ -582,10 +571,7 @@ RFD_API size_t rfd_head_packed_bytes(void) { return (size_t)H_PIECES * HPIECE; }
 // Wa [512][64] (conv1's point-feature columns), Wb [256][512], Wc [128][256]: fp32, BatchNorm folded in by the caller.
 RFD_API int rfd_head_pack(const float *Wa, const float *Wb, const float *Wc, int swa, int swb, int swc, void *packed,
                           void *stream) {
-  if (!Wa || !Wb || !Wc) {
-    rfd_set_error("rfd_head_pack: weights", hipErrorInvalidValue);
-    return (int)hipErrorInvalidValue;
-  }
+  if (!Wa || !Wb || !Wc) return rfd_invalid("rfd_head_pack: weights");
   const size_t total = rfd_head_packed_bytes() / 2;
   hipLaunchKernelGGL(head_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, Wa, Wb,
                      Wc, swa, swb, swc, (_Float16 *)packed);
@@ -601,14 +587,9 @@ RFD_API int rfd_head_scores(int M, int P, const float *x, int ldx, const void *p
   if (M <= 0) return 0;
   if (P <= 0 || P % 128 || M % P || (ldx & 3) || ((uintptr_t)x & 15) || n_cls < 1 || n_cls > 2 || !gbias || !bb || !bc ||
       !Wd || !bd || !out) {
-    rfd_set_error("rfd_head_scores: need P % 128 == 0, M % P == 0, 16-byte rows, n_cls <= 2", hipErrorInvalidValue);
-    return (int)hipErrorInvalidValue;
+    return rfd_invalid("rfd_head_scores: need P % 128 == 0, M % P == 0, 16-byte rows, n_cls <= 2");
   }
-  RfdWorkspace *ws;
-  {
-    int rc = rfd_get_workspace(&ws);
-    if (rc) return rc;
-  }
+  RFD_WORKSPACE(ws);
   HeadArgs a;
   a.M = M; a.P = P; a.ldx = ldx; a.n_cls = n_cls; a.x = x; a.packed = (const half8 *)packed; a.gbias = gbias;
   a.bb = bb; a.bc = bc; a.Wd = Wd; a.bd = bd;

@@ -126,15 +126,9 @@ RFD_API int rfd_pos_embed(int M, int N, int d, const float *x, int ldx, const fl
   if (M <= 0 || N <= 0) return 0;
   if (d < 0 || d > PE_MAX_D || (N & 3) || (ldo & 3) || rows_per_group <= 0 ||
       ((uintptr_t)out & 15) || ((uintptr_t)bias & 15) || ((uintptr_t)group & 15)) {
-    rfd_set_error("rfd_pos_embed: need d <= 8, N % 4 == 0, ldo % 4 == 0, 16-byte aligned out / bias / group",
-                  hipErrorInvalidValue);
-    return (int)hipErrorInvalidValue;
+    return rfd_invalid("rfd_pos_embed: need d <= 8, N % 4 == 0, ldo % 4 == 0, 16-byte aligned out / bias / group");
   }
-  RfdWorkspace *ws;
-  {
-    int rc = rfd_get_workspace(&ws);
-    if (rc) return rc;
-  }
+  RFD_WORKSPACE(ws);
   const int rows_per_block = 64;
   hipLaunchKernelGGL(pos_embed_kernel, dim3(ceil_div(M, rows_per_block)), dim3(PE_THREADS), 0,
                      (hipStream_t)stream, M, N, d, ldx, rows_per_group, rows_per_block, x, mask, W,
@@ -151,15 +145,10 @@ RFD_API int rfd_pos_embed_frag(int M, int N, int d, const float *x, int ldx, con
   if (M <= 0 || N <= 0) return 0;
   if (d < 1 || d > PE_MAX_D || (M % 32) || (N % 32) || rows_per_group <= 0 || (rows_per_group % 32) ||
       (rb_stride & 15) || ((uintptr_t)out & 15) || ((uintptr_t)group & 15)) {
-    rfd_set_error("rfd_pos_embed_frag: need 1 <= d <= 8, M % 32, N % 32, rows_per_group % 32, 16-byte aligned out / group",
-                  hipErrorInvalidValue);
-    return (int)hipErrorInvalidValue;
+    return rfd_invalid("rfd_pos_embed_frag: need 1 <= d <= 8, M % 32, N % 32, rows_per_group % 32, "
+                       "16-byte aligned out / group");
   }
-  RfdWorkspace *ws;
-  {
-    int rc = rfd_get_workspace(&ws);
-    if (rc) return rc;
-  }
+  RFD_WORKSPACE(ws);
   const int waves = PE_THREADS / 64;
   int blocks = ceil_div(M / 32, waves);
   const int cap = ws->num_cu * 8;                     // a few workgroups per CU; each stages W once

@@ -13,60 +13,16 @@
 // channels 8q + 4h + e of each 32-channel block; the host packs the next layer's k-order as
 // that delivery order), so bias + ReLU are applied in place and the activations never leave
 // the lane.  The last layer is reduced over the rows of a centre with lane shuffles.
-// BatchNorm (eval) is folded into W and the bias on the host.
-#include "common.h"
+// BatchNorm (eval) is folded into W and the bias on the host.  The layer pipeline and the packed-weight layout:
+// f32_wave32.h.
+#include "f32_wave32.h"
 #include "../../include/rfd_pointnet2.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using namespace f32_wave32;
 
 constexpr int SA_LDS_FLOATS = 36 * 1024;   // 144 KiB: the largest packed layer (128 x 264)
-
-__device__ __forceinline__ f32x16 mfma32(float a, float b, f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
-}
-
-// One layer: acc[b] = sum_j W[32b.., korder(j, kh)] * bin[j]; packed W in LDS as
-// [block b][j4 = j / 4][lane][4 floats].
-template <int KJ, int NB>   // KJ = k-steps (pairs of input channels, multiple of 4), NB = 32-channel output blocks
-__device__ __forceinline__ void layer(const float *s_w, const float (&bin)[KJ], f32x16 (&acc)[NB], int lane) {
-#pragma unroll
-  for (int b = 0; b < NB; ++b) acc[b] = f32x16{0.f};
-  const f32x4 *w = reinterpret_cast<const f32x4 *>(s_w) + lane;
-#pragma unroll
-  for (int j4 = 0; j4 < KJ / 4; ++j4) {
-#pragma unroll
-    for (int b = 0; b < NB; ++b) {
-      const f32x4 w4 = w[(b * (KJ / 4) + j4) * 64];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) acc[b] = mfma32(w4[e], bin[4 * j4 + e], acc[b]);
-    }
-  }
-}
-
-// bias + ReLU in place; afterwards acc[b][r] is the next layer's B operand of k-step 16b + r
-template <int NB>
-__device__ __forceinline__ void bias_relu(f32x16 (&acc)[NB], const float *__restrict__ bias, int half) {
-#pragma unroll
-  for (int b = 0; b < NB; ++b)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const f32x4 bv = *reinterpret_cast<const f32x4 *>(bias + 32 * b + 8 * q + 4 * half);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float v = acc[b][4 * q + e] + bv[e];
-        acc[b][4 * q + e] = v > 0.f ? v : 0.f;
-      }
-    }
-}
-
-__device__ __forceinline__ void stage(float *s_w, const float *__restrict__ g_w, int n_floats, int t) {
-  const f32x4 *src = reinterpret_cast<const f32x4 *>(g_w);
-  f32x4 *dst = reinterpret_cast<f32x4 *>(s_w);
-  for (int i = t; i < n_floats / 4; i += 256) dst[i] = src[i];
-}
 
 template <int KJ1, int C1, int C2, int C3>
 __global__ __launch_bounds__(256) void sa_fused_kernel(
@@ -104,17 +60,17 @@ __global__ __launch_bounds__(256) void sa_fused_kernel(
   __syncthreads();
   f32x16 a1[C1 / 32];
   layer<KJ1, C1 / 32>(s_w, bin1, a1, lane);
-  bias_relu<C1 / 32>(a1, b1, half);
+  add_bias<true, C1 / 32>(a1, b1, half);
   __syncthreads();
 
   stage(s_w, w2, C2 * C1, t);
   __syncthreads();
-  float bin2[C1 / 2];
+  float bin2[C1 / 2];                                   // spelled out, not acc_to_b<false>: see f32_wave32.h
 #pragma unroll
   for (int j = 0; j < C1 / 2; ++j) bin2[j] = a1[j >> 4][j & 15];
   f32x16 a2[C2 / 32];
   layer<C1 / 2, C2 / 32>(s_w, bin2, a2, lane);
-  bias_relu<C2 / 32>(a2, b2, half);
+  add_bias<true, C2 / 32>(a2, b2, half);
   __syncthreads();
 
   stage(s_w, w3, C3 * C2, t);
@@ -124,7 +80,7 @@ __global__ __launch_bounds__(256) void sa_fused_kernel(
   for (int j = 0; j < C2 / 2; ++j) bin3[j] = a2[j >> 4][j & 15];
   f32x16 a3[C3 / 32];
   layer<C2 / 2, C3 / 32>(s_w, bin3, a3, lane);
-  bias_relu<C3 / 32>(a3, b3, half);
+  add_bias<true, C3 / 32>(a3, b3, half);
   __syncthreads();
 
   // ---- max over the neighbours of a centre: lanes nrow..nrow+ns-1 of the same half (post-ReLU
@@ -170,10 +126,6 @@ __global__ __launch_bounds__(256) void sa_fused_kernel(
 
 }  // namespace
 
-// Packed layer layout (built by the host, rfdnet_amd/sa_fused.py): [C / 32][KJ / 4][64 lanes][4],
-// element (b, j4, lane, e) = W'[32b + (lane & 31)][korder(4 j4 + e, lane >> 5)], W' = BN-folded
-// weight, korder of layer 1 = 2j + kh (zero beyond the real input width), of layers 2 / 3 =
-// 32 (j >> 4) + 8 ((j & 15) >> 2) + 4 kh + (j & 3).
 RFD_API int rfd_sa_fused(int b, int n, int m, int nsample, int c_feat, float radius, int normalize_xyz,
                          const float *xyz, const float *new_xyz, const float *features, const int *idx,
                          int c1, int c2, int c3, const float *w1, const float *b1, const float *w2,
@@ -182,8 +134,7 @@ RFD_API int rfd_sa_fused(int b, int n, int m, int nsample, int c_feat, float rad
   const int cin = 3 + c_feat;
   const int kj1 = ((cin + 7) / 8) * 4;        // k-steps of layer 1: channel pairs, padded to 4
   if (!(nsample == 16 || nsample == 32 || nsample == 64)) {
-    rfd_set_error("rfd_sa_fused: nsample must be 16, 32 or 64", hipErrorInvalidValue);
-    return (int)hipErrorInvalidValue;
+    return rfd_invalid("rfd_sa_fused: nsample must be 16, 32 or 64");
   }
   const float inv_r = normalize_xyz ? 1.0f / radius : 1.0f;
   const int rows = m * nsample;
@@ -201,6 +152,5 @@ RFD_API int rfd_sa_fused(int b, int n, int m, int nsample, int c_feat, float rad
   RFD_SA_CASE(132, 128, 128, 256)    // SA3, SA4: 3 + 256
   RFD_SA_CASE(132, 128, 128, 128)    // vote aggregation: 3 + 256
 #undef RFD_SA_CASE
-  rfd_set_error("rfd_sa_fused: layer widths not instantiated", hipErrorInvalidValue);
-  return (int)hipErrorInvalidValue;
+  return rfd_invalid("rfd_sa_fused: layer widths not instantiated");
 }

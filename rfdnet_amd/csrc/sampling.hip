@@ -351,11 +351,9 @@ int launch_fps(int nb, int n, int m, int G, int Gw, int bs_log2, int cpb,
 int fps_impl(int b, int n, int m, const float *dataset, float *temp, int *idxs,
              float *new_xyz, void *stream) {
   if (m <= 0 || b <= 0) return 0;  // sampling_gpu.cu:73
-  if (n <= 0) { rfd_set_error("furthest_point_sampling: n <= 0", hipErrorInvalidValue); return (int)hipErrorInvalidValue; }
+  if (n <= 0) return rfd_invalid("furthest_point_sampling: n <= 0");
   hipStream_t s = (hipStream_t)stream;
-  RfdWorkspace *ws;
-  int rc = rfd_get_workspace(&ws);
-  if (rc) return rc;
+  RFD_WORKSPACE(ws);
   // geometry: G workgroups x 256 threads x PPT points cover n
   const int per_thread = ceil_div(n, FPS_THREADS);
   const int forced = ws->fps_force_ppt.load(std::memory_order_relaxed);
@@ -382,7 +380,7 @@ int fps_impl(int b, int n, int m, const float *dataset, float *temp, int *idxs,
     if (G > 64) { ppt = 32; G = ceil_div(n, FPS_THREADS * ppt); }
     if (G > 64) { ppt = 64; G = ceil_div(n, FPS_THREADS * ppt); }
   }
-  if (G > 64) { rfd_set_error("furthest_point_sampling: n > 1048576 unsupported", hipErrorInvalidValue); return (int)hipErrorInvalidValue; }
+  if (G > 64) return rfd_invalid("furthest_point_sampling: n > 1048576 unsupported");
   const int bs = ref_opt_n_threads(n);
   int bs_log2 = 0;
   while ((1 << bs_log2) < bs) ++bs_log2;
@@ -410,6 +408,7 @@ int fps_impl(int b, int n, int m, const float *dataset, float *temp, int *idxs,
     float *tp = temp + (size_t)b0 * n;
     int *ix = idxs + (size_t)b0 * m;
     float *nx = new_xyz ? new_xyz + (size_t)b0 * m * 3 : nullptr;
+    int rc;
 #define FPS_CASE(P, M) case P: rc = launch_fps<P, M>(nb, n, m, G, Gw, bs_log2, cpb, ds, tp, ix, nx, region, status, timeout_ticks, s); break;
     if (G > 1) {
       switch (ppt) {
@@ -456,10 +455,8 @@ RFD_API int rfd_test_hold_cus(int leave_free_cus, const unsigned *release_flag, 
   int rc = rfd_get_workspace(&ws);
   if (rc) return -rc;
   const int n = ws->num_cu - leave_free_cus;
-  if (!release_flag || leave_free_cus < 0 || n <= 0 || max_ms <= 0 || max_ms > 10000) {
-    rfd_set_error("rfd_test_hold_cus: arguments", hipErrorInvalidValue);
-    return -(int)hipErrorInvalidValue;
-  }
+  if (!release_flag || leave_free_cus < 0 || n <= 0 || max_ms <= 0 || max_ms > 10000)
+    return -rfd_invalid("rfd_test_hold_cus: arguments");
   // (static LDS of exactly one CU's worth: the device attribute MaxSharedMemoryPerMultiprocessor reports 64 KiB on this
   // stack, and two holders then shared a CU and left half the chip free)
   hipLaunchKernelGGL(hold_cus_kernel, dim3(n), dim3(64), 0, (hipStream_t)stream, release_flag,

@@ -83,8 +83,7 @@ RFD_API int rfd_occ_fold_rows(int K, int L, int H, const float *gb, const float 
   if (K <= 0 || L <= 0) return 0;
   if (H <= 0 || (H & 3) || ((uintptr_t)gb & 15) || ((uintptr_t)table & 15) || ((uintptr_t)row0 & 15) ||
       ((uintptr_t)sqrtv & 15) || ((uintptr_t)mean & 15) || ((uintptr_t)extra & 15) || (row0_stride & 3)) {
-    rfd_set_error("rfd_occ_fold_rows: H % 4 == 0 and 16-byte aligned tensors", hipErrorInvalidValue);
-    return (int)hipErrorInvalidValue;
+    return rfd_invalid("rfd_occ_fold_rows: H % 4 == 0 and 16-byte aligned tensors");
   }
   const size_t n = (size_t)K * (L + 1) * (H / 4);
   hipLaunchKernelGGL(occ_fold_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, K, L, H,

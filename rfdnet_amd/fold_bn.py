@@ -12,7 +12,7 @@ from . import _lib, gemm
 
 
 def folded(layer, bn=None):
-    """(W (N,K), b (N)) of `layer` (Conv1d k=1 or Linear) with `bn` folded in.
+    """(W (N,K), b (N)) of `layer` (Conv1d / Conv2d k=1 or Linear) with `bn` folded in.
     Cached on the layer, keyed by the parameter versions."""
     w = layer.weight
     stats = () if bn is None else (bn.running_mean, bn.running_var, bn.weight, bn.bias)

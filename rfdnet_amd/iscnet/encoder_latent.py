@@ -10,7 +10,7 @@ import torch
 import torch.nn as nn
 
 from .. import _lib
-from ..sa_fused import _korder_next, pack_layer
+from ..sa_fused import korder_next, pack_layer
 
 HIDDEN = 128
 LAUNCHES = 5                  # of forward() / posterior(): prep, three stages, head
@@ -46,7 +46,7 @@ class Encoder_Latent(nn.Module):
         def build():
             sd = {k: v.detach().float() for k, v in self.state_dict().items()}
             dev = sd['fc_1.weight'].device
-            korder = _korder_next(HIDDEN // 2).to(dev)
+            korder = korder_next(HIDDEN // 2).to(dev)
             order = korder.reshape(-1)                                     # lane order: position 2j + h -> channel
             l0 = torch.cat([sd['fc_pos.weight'], sd['fc_0.weight']], dim=1)[order].contiguous()
             b0 = sd['fc_pos.bias'] + sd['fc_0.bias']

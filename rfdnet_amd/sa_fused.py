@@ -6,28 +6,18 @@ import os
 
 import torch
 
-from . import _lib
+from . import _lib, fold_bn
 
 SHAPES = {(4, 64, 64, 128), (131, 128, 128, 256), (259, 128, 128, 256), (259, 128, 128, 128)}
 
 
-def _fold(conv, bn):
-    w = conv.weight.detach().reshape(conv.weight.shape[0], -1)
-    b = conv.bias.detach() if conv.bias is not None else torch.zeros(w.shape[0], device=w.device, dtype=w.dtype)
-    s = torch.rsqrt(bn.running_var + bn.eps)
-    if bn.weight is not None:
-        s = s * bn.weight.detach()
-    beta = bn.bias.detach() if bn.bias is not None else torch.zeros_like(s)
-    return w * s[:, None], ((b - bn.running_mean) * s + beta).contiguous()
-
-
-def _korder_first(kj):
+def korder_first(kj):
     j = torch.arange(kj).view(kj, 1)
     kh = torch.arange(2).view(1, 2)
     return 2 * j + kh                                              # (kj, 2)
 
 
-def _korder_next(kj):
+def korder_next(kj):
     """k-step j of a later layer reads the previous layer's accumulator register j & 15 of
     block j >> 4: channels 32 (j >> 4) + 8 ((j & 15) >> 2) + 4 kh + (j & 3)."""
     j = torch.arange(kj).view(kj, 1)
@@ -37,7 +27,7 @@ def _korder_next(kj):
 
 def pack_layer(w, korder):
     """w (C, K) -> [C/32][KJ/4][64 lanes][4]: element (b, j4, lane, e) = w[32b + (lane & 31),
-    korder[4 j4 + e, lane >> 5]] (zero where korder points past K)."""
+    korder[4 j4 + e, lane >> 5]] (zero where korder points past K): the layout of csrc/f32_wave32.h."""
     C, K = w.shape
     kj = korder.shape[0]
     assert C % 32 == 0 and kj % 4 == 0
@@ -57,9 +47,9 @@ def _packed(mlp):
     def build():
         out = []
         for li, (cv, bn) in enumerate(zip(convs, bns)):
-            w, b = _fold(cv, bn)
+            w, b = fold_bn.folded(cv, bn)
             K = w.shape[1]
-            korder = _korder_first(((K + 7) // 8) * 4) if li == 0 else _korder_next(K // 2)
+            korder = korder_first(((K + 7) // 8) * 4) if li == 0 else korder_next(K // 2)
             out += [pack_layer(w, korder), b]
         return out
     return _lib.build_once(mlp.__dict__, '_rfd_sa_packed', key, build, convs[0].weight.device)

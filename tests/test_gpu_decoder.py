@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 import torch
 
-from rfdnet_amd import synthetic
+from seeded import seeded_decoder
 
 pytestmark = pytest.mark.gpu
 LOGIT_TOL = 1e-4
@@ -26,13 +26,6 @@ def main_kernel_only(request, hip):
         yield
     finally:
         hip.lib().rfd_occ_set_tail_tiles(old)
-
-
-def seeded_decoder(seed=1234):
-    from rfdnet_amd.iscnet.occ_decoder import DecoderCBatchNorm
-    dec = DecoderCBatchNorm(dim=3, z_dim=32, c_dim=512, hidden_size=256)
-    synthetic.load_seeded(dec, seed)
-    return dec.cuda().eval()
 
 
 def test_decoder_matches_reference_fixture(hip, golden_dir):

@@ -7,10 +7,8 @@ import numpy as np
 import pytest
 import torch
 
-from rfdnet_amd import synthetic
-from rfdnet_amd.iscnet.config import Config
-
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from seeded import seeded_onet  # noqa: E402
 pytestmark = pytest.mark.gpu
 TILE = 128
 
@@ -156,26 +154,13 @@ def onet_and_fixture(hip, golden_dir):
     return fx
 
 
-def make_onet(res0, steps):
-    from rfdnet_amd.iscnet.occupancy_net import ONet
-    onet = ONet(Config({'generation': {'resolution_0': res0, 'upsampling_steps': steps}}))
-    # the reference ONet owns encoder_latent.* too: seed in the reference's key order
-    return onet
-
-
-def load_onet_seeded(onet, fx, seed=202):
-    from collections import OrderedDict
-    shapes = OrderedDict((str(n), tuple(int(x) for x in str(s).split(",")) if str(s) else ())
-                         for n, s in zip(fx["onet_names"], fx["onet_shapes"]))
-    sd = synthetic.seeded_state_dict(shapes, seed)
-    own = onet.state_dict()
-    onet.load_state_dict({k: torch.from_numpy(sd[k]) for k in own})
-    return onet.cuda().eval()
+def make_onet(fx, res0, steps):
+    return seeded_onet(fx, generation={'resolution_0': res0, 'upsampling_steps': steps})
 
 
 def test_generator_dense_grid_matches_reference(hip, onet_and_fixture):
     fx = onet_and_fixture
-    onet = load_onet_seeded(make_onet(16, 0), fx)
+    onet = make_onet(fx, 16, 0)
     grids = onet.generator.generate_grids(torch.from_numpy(fx["codes"]).cuda(), None)
     hip.device_status()
     assert grids.shape == (3, 16, 16, 16)
@@ -189,7 +174,7 @@ def test_generator_mise_grid_matches_reference(hip, onet_and_fixture, tag, res0,
     subdivision, so a vanishing fraction of fine points may be filled instead of
     evaluated -- everything else must agree to the logit tolerance."""
     fx = onet_and_fixture
-    onet = load_onet_seeded(make_onet(res0, steps), fx)
+    onet = make_onet(fx, res0, steps)
     grids = onet.generator.generate_grids(torch.from_numpy(fx["codes"]).cuda(), None).cpu().numpy()
     hip.device_status()
     ref = fx[tag + "_grid"]
@@ -211,7 +196,7 @@ def test_scatter_fused_into_the_decoder_gives_the_same_grids(hip, onet_and_fixtu
     codes = torch.from_numpy(fx["codes"]).cuda()
     out = []
     for fuse in (True, False):
-        onet = load_onet_seeded(make_onet(16, 1), fx)
+        onet = make_onet(fx, 16, 1)
         assert onet.decoder.kernel == "w8"
         onet.decoder.fuse_scatter = fuse
         assert onet.decoder.can_scatter() == fuse
@@ -297,7 +282,7 @@ def test_generate_mesh_end_to_end_scaling(hip, onet_and_fixture):
     """vertices land where generator.py:163-168 puts them: on edges of the lattice shifted by
     -1.5 padded cells, inside [-0.55 (1 + 1/(n-1)), 0.55 (1 - 1/(n-1))]"""
     fx = onet_and_fixture
-    onet = load_onet_seeded(make_onet(16, 1), fx)
+    onet = make_onet(fx, 16, 1)
     meshes = onet.generator.generate_mesh(torch.from_numpy(fx["codes"]).cuda(), None)
     assert len(meshes) == 3
     for m in meshes:
@@ -321,7 +306,7 @@ def test_mise_path_in_the_logit_bands_of_a_trained_checkpoint(hip, oracle, onet_
     from oracle import parity
     fx = onet_and_fixture
     res0, steps = 16, 1
-    onet = load_onet_seeded(make_onet(res0, steps), fx)
+    onet = make_onet(fx, res0, steps)
     gen = onet.generator
     thr = gen.logit_threshold()
     codes_h = (fx["codes"] * np.float32(scale)).astype(np.float32)

@@ -17,7 +17,7 @@ from rfdnet_amd import synthetic
 from rfdnet_amd.iscnet.config import Config
 
 from latent_f64 import bce_rowsum_f64, compute_iou, encoder_f64, kl_f64
-from test_modules_cpu import ref_keys
+from seeded import onet_arrays, seeded_onet
 
 pytestmark = pytest.mark.gpu
 
@@ -25,10 +25,6 @@ pytestmark = pytest.mark.gpu
 @pytest.fixture(scope="module")
 def fx(golden_dir):
     return np.load(os.path.join(golden_dir, "F_LAT.npz")), np.load(os.path.join(golden_dir, "F_GEN.npz"))
-
-
-def onet_arrays(fgen, seed=202):
-    return synthetic.seeded_state_dict(dict(ref_keys(fgen, "onet")), seed)
 
 
 @pytest.fixture(scope="module")
@@ -42,11 +38,7 @@ def encoder(hip, fx):
 
 
 def make_onet(fgen, threshold=0.5):
-    from rfdnet_amd.iscnet.occupancy_net import ONet
-    onet = ONet(Config({'data': {'threshold': threshold, 'latent_encoder': True},
-                        'generation': {'resolution_0': 16, 'upsampling_steps': 0}}))
-    onet.load_state_dict({k: torch.from_numpy(v) for k, v in onet_arrays(fgen).items()})
-    return onet.cuda().eval()
+    return seeded_onet(fgen, generation={'upsampling_steps': 0}, data={'threshold': threshold, 'latent_encoder': True})
 
 
 def count_calls(hip, monkeypatch):

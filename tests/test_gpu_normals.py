@@ -18,21 +18,10 @@ from rfdnet_amd import synthetic
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from normals_f64 import contract, input_grad, normals_of  # noqa: E402
+from seeded import seeded_decoder, seeded_onet  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-4
-
-
-def seeded_onet(fx_gen, seed=202, res0=16, steps=1, with_normals=False):
-    from rfdnet_amd.iscnet.config import Config
-    from rfdnet_amd.iscnet.occupancy_net import ONet
-    onet = ONet(Config({'generation': {'resolution_0': res0, 'upsampling_steps': steps, 'with_normals': with_normals}}))
-    shapes = OrderedDict((str(n), tuple(int(x) for x in str(s).split(",")) if str(s) else ())
-                         for n, s in zip(fx_gen["onet_names"], fx_gen["onet_shapes"]))
-    sd = synthetic.seeded_state_dict(shapes, seed)
-    own = onet.state_dict()
-    onet.load_state_dict({k: torch.from_numpy(sd[k]) for k in own})
-    return onet.cuda().eval()
 
 
 def dec_sd(dec):
@@ -106,13 +95,6 @@ def ragged_case(K=37, seed=3):
     return verts, vend, z, c
 
 
-def seeded_decoder(seed=1234):
-    from rfdnet_amd.iscnet.occ_decoder import DecoderCBatchNorm
-    dec = DecoderCBatchNorm(dim=3, z_dim=32, c_dim=512, hidden_size=256)
-    synthetic.load_seeded(dec, seed)
-    return dec.cuda().eval()
-
-
 def test_normals_ragged_meshes_against_float64(hip):
     dec = seeded_decoder(1234)
     verts, vend, z, c = ragged_case()
@@ -136,8 +118,8 @@ def test_normals_point_independence_bit_for_bit(hip):
 def test_generator_with_normals_keeps_the_meshes_and_orients_outward(hip, fx):
     nrm, gen = fx
     codes = torch.from_numpy(gen["codes"]).cuda()
-    plain = seeded_onet(gen, with_normals=False).generator.generate_mesh(codes, None)
-    onet = seeded_onet(gen, with_normals=True)
+    plain = seeded_onet(gen, generation={'with_normals': False}).generator.generate_mesh(codes, None)
+    onet = seeded_onet(gen, generation={'with_normals': True})
     g = onet.generator
     meshes = g.generate_mesh(codes, None)
     hip.device_status()

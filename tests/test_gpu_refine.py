@@ -18,24 +18,9 @@ from rfdnet_amd import synthetic
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from refine_f64 import loss_f64, refine_f64  # noqa: E402
+from seeded import reference_draws, seeded_onet  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-
-
-def reference_draws(n_faces, steps, seed):
-    np.random.seed(seed)
-    return np.stack([np.random.dirichlet((0.5, 0.5, 0.5), size=n_faces) for _ in range(steps)]).astype(np.float32)
-
-
-def seeded_onet(fx_gen, seed=202, **generation):
-    from rfdnet_amd.iscnet.config import Config
-    from rfdnet_amd.iscnet.occupancy_net import ONet
-    onet = ONet(Config({'generation': dict({'resolution_0': 16, 'upsampling_steps': 1}, **generation)}))
-    shapes = OrderedDict((str(n), tuple(int(x) for x in str(s).split(",")) if str(s) else ())
-                         for n, s in zip(fx_gen["onet_names"], fx_gen["onet_shapes"]))
-    sd = synthetic.seeded_state_dict(shapes, seed)
-    onet.load_state_dict({k: torch.from_numpy(sd[k]) for k in onet.state_dict()})
-    return onet.cuda().eval()
 
 
 @pytest.fixture(scope="module")

@@ -92,6 +92,11 @@ def test_shipped_kernels_carry_no_wrong_result_switch_and_the_ablation_patch_reb
             for token in ("v_pk_max_u16", "v_fma_mix_f32", "0x7bffu"):
                 assert token not in text, (name, token)
             assert "65504.f" not in text, name                          # ... and so has the fp32 form of the limit
+        # the exact-fp32 matrix instruction of the wave-of-32 kernels has one wrapper ...
+        if name != "f32_wave32.h":
+            assert "mfma_f32_32x32x2f32" not in text, name
+        # ... and a launcher's failed argument check one spelling: rfd_invalid (common.h), not the two lines it stands for
+        assert not re.search(r"rfd_set_error\([^\n]*\n[^\n]*hipErrorInvalidValue", text), name
         # the status flags are named (include/rfd_pointnet2.h): no bare 1u / 2u / 4u where one is raised
         for m in re.finditer(r"\b(?:atomicOr|flag_f16_range|flag_out_range)\(([^;{]*)\);", text):
             assert not re.search(r",\s*[124]u\s*$", m.group(1)), (name, m.group(0))

@@ -10,6 +10,7 @@ from rfdnet_amd import synthetic
 from rfdnet_amd.iscnet.config import Config
 
 from latent_f64 import bce_rowsum_f64, compute_iou, encoder_f64, kl_f64
+from seeded import decoder_arrays, onet_arrays
 from test_modules_cpu import my_keys, ref_keys
 
 
@@ -21,11 +22,6 @@ def flat(golden_dir):
 @pytest.fixture(scope="module")
 def fgen(golden_dir):
     return np.load(os.path.join(golden_dir, "F_GEN.npz"))
-
-
-def seeded_onet_arrays(fgen, seed=202):
-    """the F_GEN ONet's parameters (seeded in the reference's key order, encoder_latent.* first) as numpy"""
-    return synthetic.seeded_state_dict(dict(ref_keys(fgen, "onet")), seed)
 
 
 def test_onet_with_latent_encoder_has_the_reference_keys_in_order(fgen):
@@ -46,7 +42,7 @@ def test_a_reference_checkpoint_keeps_its_latent_encoder_tensors(fgen):
     """load_weight drops keys the network does not own: with the encoder enabled completion.encoder_latent.* stay"""
     import torch
     from rfdnet_amd.iscnet.network import ISCNet
-    sd = {"module.completion." + k: torch.from_numpy(v) for k, v in seeded_onet_arrays(fgen).items()}
+    sd = {"module.completion." + k: torch.from_numpy(v) for k, v in onet_arrays(fgen).items()}
     plain = ISCNet(Config())
     plain.load_weight(sd)
     assert plain.completion.encoder_latent is None
@@ -59,7 +55,7 @@ def test_a_reference_checkpoint_keeps_its_latent_encoder_tensors(fgen):
 
 
 def test_restatement_agrees_with_the_float64_run_of_the_reference_modules(flat, fgen):
-    sd = {k[len("encoder_latent."):]: v for k, v in seeded_onet_arrays(fgen).items() if k.startswith("encoder_latent.")}
+    sd = {k[len("encoder_latent."):]: v for k, v in onet_arrays(fgen).items() if k.startswith("encoder_latent.")}
     mean, logstd = encoder_f64(sd, flat["points"], flat["occ"], fgen["codes"])
     assert np.abs(mean - flat["mean64"]).max() <= 1e-12
     assert np.abs(logstd - flat["logstd64"]).max() <= 1e-12
@@ -68,7 +64,7 @@ def test_restatement_agrees_with_the_float64_run_of_the_reference_modules(flat, 
     assert np.abs(z - flat["z64"]).max() <= 1e-12
     # the decoder's restatement (tests/dec_f64.py) closes the loop: BCE at that z, and the lattice logits
     from dec_f64 import decoder_f64
-    dsd = {k[len("decoder."):]: v for k, v in seeded_onet_arrays(fgen).items() if k.startswith("decoder.")}
+    dsd = decoder_arrays(fgen)
     bce = bce_rowsum_f64(decoder_f64(dsd, flat["points"], z, fgen["codes"]), flat["occ"])
     assert np.abs(bce - flat["bce64"]).max() <= 1e-12 * flat["bce64"].max()
     # the fixture is self-consistent: fp32 records within their own stated deviation, the loss is the two means

@@ -2,7 +2,6 @@
 config, PLY output, demo flag, and the F_NRM fixture against the float64 gradient (tests/normals_f64.py)."""
 import os
 import sys
-from collections import OrderedDict
 
 import numpy as np
 import pytest
@@ -28,23 +27,14 @@ def test_normals_entry_point_is_declared_and_bound():
     assert "rfd_occ_normals_w8" in _lib.exported_symbols()
 
 
-def onet_decoder_sd(seed=202):
-    """the F_GEN ONet's decoder parameters (seeded in the reference's key order) as numpy, decoder key names"""
-    from rfdnet_amd import synthetic
-    fx = np.load(os.path.join(ROOT, "tests", "golden", "F_GEN.npz"))
-    shapes = OrderedDict((str(n), tuple(int(x) for x in str(s).split(",")) if str(s) else ())
-                         for n, s in zip(fx["onet_names"], fx["onet_shapes"]))
-    sd = synthetic.seeded_state_dict(shapes, seed)
-    return {k[len("decoder."):]: v for k, v in sd.items() if k.startswith("decoder.")}
-
-
 def test_fixture_reference_normals_agree_with_the_float64_gradient():
     """F_NRM (the reference's estimate_normals, fp32 autograd on the CPU) vs the float64 restatement: the fixture and the
     helper check each other.  Vertices where fp32 itself is > 1e-4 from float64 are the contract's exception set."""
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     from normals_f64 import input_grad, normals_of
+    from seeded import decoder_arrays
     fx = np.load(os.path.join(ROOT, "tests", "golden", "F_NRM.npz"))
-    sd = onet_decoder_sd(int(fx["seed"]))
+    sd = decoder_arrays(np.load(os.path.join(ROOT, "tests", "golden", "F_GEN.npz")), int(fx["seed"]))
     vend = fx["vend"]
     err = []
     for k in range(len(vend) - 1):

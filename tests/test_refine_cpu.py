@@ -10,36 +10,19 @@ import numpy as np
 import pytest
 import torch
 
-from rfdnet_amd import synthetic
-
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from refine_f64 import loss_f64, refine_f64  # noqa: E402
+from seeded import reference_draws, seeded_onet  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW_ENTRIES = ["rfd_refine_sample", "rfd_refine_face_backward", "rfd_refine_vertex_step", "rfd_refine_dirichlet"]
 
 
-def reference_draws(n_faces, steps, seed):
-    """what generator.py:259 draws in `steps` steps of one mesh after np.random.seed(seed)"""
-    np.random.seed(seed)
-    return np.stack([np.random.dirichlet((0.5, 0.5, 0.5), size=n_faces) for _ in range(steps)]).astype(np.float32)
-
-
-def seeded_decoder_sd(fx_gen, seed):
-    from rfdnet_amd.iscnet.config import Config
-    from rfdnet_amd.iscnet.occupancy_net import ONet
-    onet = ONet(Config({'generation': {'resolution_0': 16, 'upsampling_steps': 1}}))
-    shapes = OrderedDict((str(n), tuple(int(x) for x in str(s).split(",")) if str(s) else ())
-                         for n, s in zip(fx_gen["onet_names"], fx_gen["onet_shapes"]))
-    sd = synthetic.seeded_state_dict(shapes, seed)
-    onet.load_state_dict({k: torch.from_numpy(sd[k]) for k in onet.state_dict()})
-    return onet, OrderedDict((k, v.detach().numpy()) for k, v in onet.decoder.state_dict().items())
-
-
 @pytest.fixture(scope="module")
 def fx(golden_dir):
     ref, gen = np.load(os.path.join(golden_dir, "F_REF.npz")), np.load(os.path.join(golden_dir, "F_GEN.npz"))
-    onet, sd = seeded_decoder_sd(gen, 202)
+    onet = seeded_onet(gen, 202)
+    sd = OrderedDict((k, v.detach().cpu().numpy()) for k, v in onet.decoder.state_dict().items())
     return ref, gen["codes"][int(ref["code_index"])], np.zeros(onet.z_dim, np.float32), sd
 
 
