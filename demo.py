@@ -37,7 +37,9 @@ def build_parser():
                          "box_label_mask); the scene then goes through ISCNet.evaluate and its box AP / recall at IoU "
                          "0.25 and 0.5 are printed.  If it also holds object_points, object_points_occ and "
                          "object_voxels, the completion loss and the mean voxel IoU are printed too (needs a "
-                         "checkpoint with completion.encoder_latent.* to mean anything)")
+                         "checkpoint with completion.encoder_latent.* to mean anything).  If it holds vote_label and "
+                         "vote_label_mask, the loss dictionary of the reference's test mode is printed (detection loss; "
+                         "with point_instance_labels and object_instance_labels also PointSeg's mask loss)")
     ap.add_argument("--mean_size_npz", type=str, default=None,
                     help="class mean sizes (the reference's datasets/scannet/scannet_means.npz); default: "
                          "$RFD_MEAN_SIZE_NPZ or that path relative to the working directory")
@@ -80,6 +82,9 @@ def main():
     completion_keys = ('object_points', 'object_points_occ', 'object_voxels')
     gt = np.load(args.gt) if args.mode == "test" and args.gt else None
     completion = gt is not None and all(k in gt.files for k in completion_keys)
+    loss_keys = ('vote_label', 'vote_label_mask')
+    instance_keys = ('point_instance_labels', 'object_instance_labels')
+    losses = gt is not None and all(k in gt.files for k in loss_keys)
     if completion:
         cfg.config['data']['latent_encoder'] = True                      # before the weights are loaded: its keys are kept
     net = ISCNet(cfg)
@@ -109,7 +114,12 @@ def main():
             a = np.asarray(gt[k], dtype=np.float32)
             per_scan = 3 if k == 'object_points' else 2 if k == 'object_points_occ' else 4
             data[k] = torch.from_numpy(a[None] if a.ndim == per_scan else a).cuda()
-        end_points, ids, meshes, records = net.evaluate(data, completion=completion)
+        for k in (loss_keys + instance_keys if losses and all(k in gt.files for k in instance_keys) else
+                  loss_keys if losses else ()):
+            a = np.asarray(gt[k])
+            per_scan = 2 if k == 'vote_label' else 1
+            data[k] = torch.from_numpy(a[None] if a.ndim == per_scan else a).cuda()
+        end_points, ids, meshes, records = net.evaluate(data, completion=completion, losses=losses)
     else:
         end_points, ids, meshes = net.generate(data, selection=args.selection)
     torch.cuda.synchronize()
@@ -125,6 +135,8 @@ def main():
         print('completion loss: %.4f; mean voxel IoU over %d proposals: %s'
               % (float(end_points['completion_loss']), ids.shape[1],
                  'n/a' if stats is None or not len(stats['iou']) else '%.4f' % float(np.nanmean(stats['iou']))))
+    if 'loss' in end_points:
+        print('loss: %s' % {k: round(float(v), 6) for k, v in end_points['loss'].items()})
     box = keep = None
     if 'parsed_predictions' in end_points:
         box = end_points['parsed_predictions']['box_params'][0].cpu().numpy()

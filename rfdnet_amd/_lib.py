@@ -17,7 +17,7 @@ _fl = C.c_float
 _sz = C.c_size_t
 
 # name -> (restype, argtypes[, OPTIONAL]): exactly the prototypes of include/rfd_pointnet2.h / rfd_occ.h /
-# rfd_chamfer.h / rfd_eval.h / rfd_latent.h.  OPTIONAL marks the test hooks, which a deployment build (RFD_NO_TEST_HOOKS=1, build.py)
+# rfd_chamfer.h / rfd_eval.h / rfd_latent.h / rfd_loss.h.  OPTIONAL marks the test hooks, which a deployment build (RFD_NO_TEST_HOOKS=1, build.py)
 # leaves out.
 OPTIONAL = "optional"
 ABI = {
@@ -90,6 +90,12 @@ ABI = {
     "rfd_latent_head": (_i, [_i, _i, _f, _f, _f, _f, _f, _f, _f, _f, _f]),
     "rfd_bce_logits_rowsum": (_i, [_i, _i, _f, _i, _f, _i, _f, _f]),
     "rfd_voxel_iou": (_i, [_i, _i, _f, _i, _fl, _f, _f, _f, _f]),
+    "rfd_vote_loss_partial": (_i, [_i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _f]),
+    "rfd_proposal_loss_partial": (_i, [_i, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _f, _f, C.POINTER(C.c_int), _f, _i, _f, _f,
+                                       _f, _f, _f, _f, _f, _f, _f, _f, _i, _f, _f]),
+    "rfd_detection_loss_finish": (_i, [_i, _i, _i, _f, _f, _f]),
+    "rfd_mask_loss_partial": (_i, [_i, _i, _f, _f, _i, _f, _f, _f, _f]),
+    "rfd_mask_loss_finish": (_i, [_i, _i, _fl, _f, _f, _f]),
     "rfd_last_error_string": (C.c_char_p, []),
     "rfd_build_arch": (C.c_char_p, []),
     "rfd_device_status": (_i, []),

@@ -20,9 +20,9 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import (occupancy_net, pointnet2backbone, proposal_module,  # noqa: F401  (register)
+from . import (loss, occupancy_net, pointnet2backbone, proposal_module,  # noqa: F401  (register)
                skip_propagation, vote_module)
-from .registers import METHODS, MODULES
+from .registers import LOSSES, METHODS, MODULES
 
 
 class _StageFlag(Exception):
@@ -55,6 +55,8 @@ class ISCNet(nn.Module):
             if cls is None:
                 raise ModuleNotFoundError('unknown module %r' % net_spec['method'])
             self.add_module(phase_name, cls(cfg, None))
+            # the phase's loss function (network.py:49-50): a plain attribute, no parameter and no state_dict key
+            setattr(self, phase_name + '_loss', LOSSES.get(net_spec.get('loss'), 'Null')(net_spec.get('weight', 1)))
 
     def load_weight(self, pretrained_model):
         """state_dict with the reference's key names (optionally `module.`-prefixed)."""
@@ -120,9 +122,11 @@ class ISCNet(nn.Module):
             return ids
         raise ValueError(selection)
 
-    def object_codes(self, end_points, proposal_features, ids, point_clouds):
+    def object_codes(self, end_points, proposal_features, ids, point_clouds, labels=None):
         """gather per-proposal features / centres / headings and run skip
-        propagation (demo.py:236-258) -> (B*K, c_dim)."""
+        propagation (demo.py:236-258) -> (B*K, c_dim).
+        labels: (point_instance_labels (B,N), proposal_instance_labels (B,K), sink) -- the test mode's call of
+        SkipPropagation.forward (network.py:123-124); its mask loss goes to sink['mask_loss']."""
         dev = end_points['center'].device
         idx = ids[..., 0]
         feats = torch.gather(proposal_features, 2, idx.unsqueeze(1).expand(-1, 128, -1))
@@ -136,7 +140,11 @@ class ISCNet(nn.Module):
             heading_residual = torch.gather(residuals, 2, heading_class.unsqueeze(-1)).squeeze(2)
             angles = dc.class2angle_cuda(heading_class, heading_residual)
             angles = torch.gather(angles, 1, idx)
-            obj = self.skip_propagation.generate(centers.contiguous(), angles, feats, point_clouds)
+            if labels is not None:
+                obj, labels[2]['mask_loss'] = self.skip_propagation(centers.contiguous(), angles, feats, point_clouds,
+                                                                    labels[0], labels[1])
+            else:
+                obj = self.skip_propagation.generate(centers.contiguous(), angles, feats, point_clouds)
         B, C, K = obj.size()
         return obj.transpose(1, 2).contiguous().view(B * K, C)
 
@@ -168,7 +176,40 @@ class ISCNet(nn.Module):
         out = self.reconstruct(end_points, proposal_features, ids, pc, return_grids=return_grids, hook=hook)
         return end_points, ids, out
 
-    def evaluate(self, data, fit=True, ap_iou_thresh=(0.25, 0.5), timing=False, completion=False, completion_eps=None):
+    def loss(self, est_data, gt_data):
+        """network.py:473-487: est_data = (end_points, completion_loss (1,2): [completion loss, mask loss], ...) -> the
+        detection dictionary, plus completion_loss / mask_loss and the `total` update when the phase is `completion`."""
+        end_points, completion_loss = est_data[:2]
+        total_loss = self.detection_loss(end_points, gt_data, self.cfg.dataset_config)
+        if self.cfg.config[self.cfg.config['mode']]['phase'] == 'completion':
+            completion_loss = self.completion_loss(completion_loss)
+            total_loss = {**total_loss, 'completion_loss': completion_loss['completion_loss'],
+                          'mask_loss': completion_loss['mask_loss']}
+            total_loss['total'] = total_loss['total'] + completion_loss['total_loss']
+        return total_loss
+
+    def _generate_with_labels(self, data, hook, sink):
+        """generate(selection='nms') of the test mode with losses: the proposal -> ground-truth pairing is made BEFORE skip
+        propagation, so the proposals' instance labels exist when the codes are built (network.py:97, 123-124)."""
+        from . import evaluation
+        from .. import _lib
+        pc = data['point_clouds']
+        end_points, proposal_features = self.detect(pc)
+        ids = self.select_proposals(end_points, 'nms', pc)
+        if ids.shape[1] == 0:
+            _lib.raise_status(_lib.stream_status_bits())
+            return end_points, ids, []
+        sink['pairs'] = pairs = evaluation.proposal_to_gt(end_points, data, ids)
+        labels = None
+        if self.cfg.config['data']['skip_propagate'] and 'point_instance_labels' in data and \
+                'object_instance_labels' in data:
+            wanted = torch.gather(data['object_instance_labels'].to(pc.device), 1, pairs[:, :, 1])
+            labels = (data['point_instance_labels'], wanted, sink)
+        out = self.reconstruct(end_points, proposal_features, ids, pc, hook=hook, labels=labels)
+        return end_points, ids, out
+
+    def evaluate(self, data, fit=True, ap_iou_thresh=(0.25, 0.5), timing=False, completion=False, completion_eps=None,
+                 losses=False):
         """The tail of the reference's `generate` in test mode (network.py:85-177): detection and completion with
         selection='nms', then (fit) the box refinement of fit_mesh_to_scan, then the evaluation records of the --
         refined -- boxes against the ground-truth labels in `data` (center_label, heading_class_label,
@@ -181,13 +222,26 @@ class ISCNet(nn.Module):
         proposal is paired with its nearest ground-truth box (evaluation.proposal_to_gt), that box's occupancy samples
         are gathered (prepare_data) and ONet.compute_loss is run on them (completion_eps: its `eps`).  Results:
         end_points['completion_loss'] (0-d device tensor), ['proposal_to_gt'] (B,K',3) and ['iou_stats'] =
-        {'cls','iou'} numpy arrays over the B*K' proposals (None without object_voxels).  The return tuple is the same."""
+        {'cls','iou'} numpy arrays over the B*K' proposals (None without object_voxels).  The return tuple is the same.
+        losses=True adds the loss dictionary the reference prints beside the metrics (testing.py:63-68): `data` also
+        carries vote_label (B,N,9) and vote_label_mask (B,N), and for the mask loss point_instance_labels (B,N) and
+        object_instance_labels (B,G) (absent: mask loss 0).  end_points['loss'] = ISCNet.loss(...): DetectionLoss's thirteen
+        keys, completion_loss, mask_loss, and `total` with ONet_Loss's weight * (completion + 100 mask) added."""
         from . import evaluation
         captured = {}
         hook = (lambda codes, cls: captured.update(codes=codes, cls=cls)) if completion else None
-        end_points, ids, meshes = self.generate(data, selection='nms', hook=hook)
+        if losses:
+            end_points, ids, meshes = self._generate_with_labels(data, hook, captured)
+        else:
+            end_points, ids, meshes = self.generate(data, selection='nms', hook=hook)
         if completion:
             self._completion_block(end_points, data, ids, captured, completion_eps)
+        if losses:
+            dev = end_points['center'].device
+            zero = torch.zeros((), device=dev)
+            value = torch.stack([end_points.get('completion_loss', zero).float(),
+                                 captured.get('mask_loss', zero).float()]).unsqueeze(0)
+            end_points['loss'] = self.loss((end_points, value), data)
         parsed = end_points['parsed_predictions']
         eval_dict = {'pred_mask': end_points['pred_mask']}
         if fit and len(meshes):
@@ -208,7 +262,7 @@ class ISCNet(nn.Module):
             end_points['completion_loss'] = torch.zeros((), device=dev)
             end_points['proposal_to_gt'] = ids.new_zeros(ids.shape[0], 0, 3)
             return
-        pairs = evaluation.proposal_to_gt(end_points, data, ids)
+        pairs = captured['pairs'] if 'pairs' in captured else evaluation.proposal_to_gt(end_points, data, ids)
         on_dev = {k: data[k].to(dev) for k in ('object_points', 'object_points_occ')}
         points, occ = evaluation.prepare_data(on_dev, pairs)
         voxels = data.get('object_voxels')
@@ -224,18 +278,19 @@ class ISCNet(nn.Module):
             iou = evaluation.voxel_iou(terms['voxel_logits'], self.completion.logit_threshold(), gt)
             end_points['iou_stats'] = {'cls': pairs[:, :, 2].reshape(-1).cpu().numpy(), 'iou': iou.cpu().numpy()}
 
-    def reconstruct(self, end_points, proposal_features, ids, pc, return_grids=False, hook=None):
+    def reconstruct(self, end_points, proposal_features, ids, pc, return_grids=False, hook=None, labels=None):
         """skip propagation -> object codes -> occupancy completion for the selected proposals, with the status
         reads that must follow (see complete()).  A split-precision GEMM activation beyond the f16 range at the
         default scale (_lib.STATUS_GEMM_RANGE, skip-propagation encoder) does not fail the scene either: the stage is run
         again at the fallback scale (gemm.lower_scale), and only a second flag raises.
-        hook(codes, cls): called before the completion (the benchmark installs its copy scheduling there)."""
+        hook(codes, cls): called before the completion (the benchmark installs its copy scheduling there).
+        labels: see object_codes()."""
         from .. import _lib, gemm
         for attempt in (0, 1):
             # the GEMM scale THIS attempt runs at: the model (and gemm.SA) is shared by every scene in flight, so
             # another scene may lower it while this one runs (ADVICE round 4)
             sa_used = gemm.SA
-            codes = self.object_codes(end_points, proposal_features, ids, pc)
+            codes = self.object_codes(end_points, proposal_features, ids, pc, labels)
             cls = self.cls_codes(end_points, ids)
             # A snapshot of the stream's status word is taken HERE, before the completion, without waiting: a GEMM that
             # overflowed has clipped the codes, and a decoder run on clipped codes could raise ITS range flag -- the

@@ -128,6 +128,58 @@ class PointNetEncoder(nn.Module):
         return torch.cat([x, pointfeat], 1), trans, trans_feat
 
 
+def feature_transform_reguliarzer(trans):
+    """mean_k || T_k (T_k^t - I) ||_F, as the reference writes it (pointseg.py:132-139; its spelling)"""
+    d = trans.size()[1]
+    eye = torch.eye(d, device=trans.device, dtype=trans.dtype)[None, :, :]
+    return torch.mean(torch.norm(torch.bmm(trans, trans.transpose(2, 1) - eye), dim=(1, 2)))
+
+
+def mask_loss_rows(logp, grouped_labels, proposal_labels, trans_feat, scale=0.001):
+    """PointSeg's mask loss of the test mode in two launches (csrc/det_loss.hip, include/rfd_loss.h):
+    nll_loss(logp, grouped_labels == proposal_labels) + scale * feature_transform_reguliarzer(trans_feat), a 0-d tensor.
+    logp (Kp,P,2) f32 log-probabilities, grouped_labels (Kp,P) the instance label of every grouped point (a row-strided
+    view is read in place), proposal_labels (Kp,) the proposals' instance labels, trans_feat (Kp,64,64)."""
+    from .. import _lib
+    if not logp.is_cuda:
+        raise RuntimeError("CPU not supported")
+    dev = logp.device
+    Kp, P, k = logp.shape
+    assert k == 2 and trans_feat.shape == (Kp, 64, 64) and grouped_labels.shape == (Kp, P)
+    logp = logp.float().contiguous()
+    lab = grouped_labels.to(dev).float()
+    if lab.stride(1) != 1 or (Kp > 1 and lab.stride(0) < P):
+        lab = lab.contiguous()
+    want = proposal_labels.to(dev).reshape(Kp).long().contiguous()
+    trans_feat = trans_feat.float().contiguous()
+    partial = torch.empty(Kp, 2, dtype=torch.float64, device=dev)
+    out = torch.empty(1, dtype=torch.float32, device=dev)
+    _lib.call("rfd_mask_loss_partial", dev, Kp, P, logp.data_ptr(), lab.data_ptr(), int(lab.stride(0)) if Kp > 1 else P,
+              want.data_ptr(), trans_feat.data_ptr(), partial.data_ptr())
+    _lib.call("rfd_mask_loss_finish", dev, Kp, P, float(scale), partial.data_ptr(), out.data_ptr())
+    return out[0]
+
+
+class get_loss(nn.Module):
+    """pointseg.py:168-177: forward(pred (M,2) log-probabilities, target (M,) 0/1, trans_feat (Kp,64,64), weight) with
+    M = Kp * P -> the mask loss on the device.  No parameters."""
+
+    def __init__(self, mat_diff_loss_scale=0.001):
+        super().__init__()
+        self.mat_diff_loss_scale = mat_diff_loss_scale
+
+    def forward(self, pred, target, trans_feat, weight):
+        if weight is not None:
+            raise NotImplementedError("get_loss: class weights are not supported (the reference passes None)")
+        if not pred.is_cuda:
+            raise RuntimeError("CPU not supported")
+        Kp = trans_feat.shape[0]
+        P = pred.shape[0] // Kp
+        assert pred.shape == (Kp * P, 2) and target.numel() == Kp * P
+        ones = torch.ones(Kp, dtype=torch.int64, device=pred.device)
+        return mask_loss_rows(pred.view(Kp, P, 2), target.view(Kp, P), ones, trans_feat, self.mat_diff_loss_scale)
+
+
 class PointSeg(nn.Module):
     def __init__(self, num_class, channel):
         super().__init__()

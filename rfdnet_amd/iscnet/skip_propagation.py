@@ -10,7 +10,7 @@ from torch import nn
 from .. import pos_embed
 from ..pointnet2_ops.pointnet2_modules import STN_Group
 from .layers import ResnetPointnet
-from .pointseg import PointSeg
+from .pointseg import PointSeg, get_loss
 from .registers import MODULES
 
 
@@ -25,6 +25,7 @@ class SkipPropagation(nn.Module):
         self.encoder = ResnetPointnet(c_dim=data['c_dim'], dim=self.input_feature_dim + 3 + 128,
                                       hidden_dim=data['hidden_dim'])
         self.point_seg = PointSeg(num_class=2, channel=self.input_feature_dim + 3)
+        self.mask_loss_func = get_loss()                       # no parameters: the state_dict is unchanged
 
     def _break_up_pc(self, pc):
         xyz = pc[..., 0:3].contiguous()
@@ -32,16 +33,42 @@ class SkipPropagation(nn.Module):
                     if pc.size(-1) > 3 else None)
         return xyz, features
 
+    def forward(self, box_xyz, box_orientations, box_feature, input_point_cloud, point_instance_labels,
+                proposal_instance_labels):
+        """The ground-truth-dependent path of the test mode (:84-137): generate() with the instance-label channel filled
+        -- point_instance_labels (B,N), proposal_instance_labels (B,K) -- -> (object codes (B, c_dim, K), bit-identical
+        to generate()'s; PointSeg's mask loss, a 0-d tensor: pointseg.mask_loss_rows on the grouped labels).  Values
+        only, device tensors only."""
+        if not input_point_cloud.is_cuda:
+            raise RuntimeError("CPU not supported")
+        with torch.no_grad():
+            return self._codes(box_xyz, box_orientations, box_feature, input_point_cloud,
+                               (point_instance_labels, proposal_instance_labels))
+
     def generate(self, box_xyz, box_orientations, box_feature, input_point_cloud):
         """box_xyz (B,K,3), box_orientations (B,K), box_feature (B,128,K),
         input_point_cloud (B,N,3+f) -> object codes (B, c_dim, K)."""
+        return self._codes(box_xyz, box_orientations, box_feature, input_point_cloud, None)
+
+    def _codes(self, box_xyz, box_orientations, box_feature, input_point_cloud, labels):
         xyz, features = self._break_up_pc(input_point_cloud)
-        # the instance-label channel is all zeros at generation time (:52-53)
-        features = torch.cat([features, torch.zeros_like(features)], dim=1)
+        if labels is None:
+            # the instance-label channel is all zeros at generation time (:52-53)
+            features = torch.cat([features, torch.zeros_like(features)], dim=1)
+        else:
+            features = torch.cat([features, labels[0].to(features.device).unsqueeze(1).to(features.dtype)], dim=1)
         rows, gfeat = self.stn.forward_rows(xyz, features, box_xyz, box_orientations)   # (B*K,P,3), (B,C,K,P)
         B, _, K, P = gfeat.size()
         inp = torch.cat([rows, gfeat[:, 0].reshape(B * K, P, 1)], dim=2)                  # (B*K, P, 3+f)
-        seg_pred, _ = self.point_seg.forward_rows(inp)
+        seg_pred, trans_feat = self.point_seg.forward_rows(inp)
+        if labels is not None:
+            from .pointseg import mask_loss_rows
+            return self._encode(inp, seg_pred, box_feature, B, K, P), mask_loss_rows(
+                seg_pred.view(B * K, P, 2), gfeat[:, 1].reshape(B * K, P), labels[1].reshape(B * K), trans_feat,
+                self.mask_loss_func.mat_diff_loss_scale)
+        return self._encode(inp, seg_pred, box_feature, B, K, P)
+
+    def _encode(self, inp, seg_pred, box_feature, B, K, P):
         mask = torch.argmax(seg_pred.view(B * K * P, 2), dim=1).view(B * K, P, 1)
         # encoder input = cat([points, box feature repeated over the points]) * mask.
         # The 128 box-feature channels are one vector per proposal, so their share

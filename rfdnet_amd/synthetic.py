@@ -144,3 +144,50 @@ def object_occupancy(boxes, n_points=2048, seed=11, fill=0.9):
     lattice = np.stack(np.meshgrid(lin, lin, lin, indexing='ij'), axis=-1).reshape(1, -1, 3)
     voxels = inside(np.broadcast_to(lattice, (G, 4096, 3))).reshape(G, 16, 16, 16)
     return pts.astype(np.float32), inside(pts).astype(np.float32), voxels.astype(np.float32)
+
+
+def scene_labels(pc, boxes, cls, G=64, mean_size_arr=None, margin=0.02):
+    """The dataloader-shaped label dictionary (numpy, batch of one) of a synthetic_scene(return_boxes=True) scene: what
+    ISCNet.evaluate(losses=True) reads beside the point cloud.  Box g fills label row g of G; the padded rows are zero.
+      center_label (1,G,3) f32, heading_class_label / size_class_label / sem_cls_label (1,G) int64,
+      heading_residual_label (1,G) f32, size_residual_label (1,G,3) f32, box_label_mask (1,G) f32:
+        ScanNet's angle2class (12 bins) and size2class (one size cluster per class, residual = size - mean size);
+      vote_label (1,N,9) f32, vote_label_mask (1,N) int64: a point within `margin` of a cuboid votes for its centre
+        (centre - point, three copies); a point in several cuboids votes for the first;
+      point_instance_labels (1,N) int64, object_instance_labels (1,G) int64: instance id = row + 1, 0 = no object."""
+    pc = np.asarray(pc)
+    boxes = np.asarray(boxes, dtype=np.float64)
+    cls = np.asarray(cls, dtype=np.int64)
+    n = boxes.shape[0]
+    assert n <= G and pc.ndim == 2
+    if mean_size_arr is None:
+        mean_size_arr = np.full((8, 3), 0.8)
+    mean_size_arr = np.asarray(mean_size_arr, dtype=np.float64)
+    N = pc.shape[0]
+    out = {'center_label': np.zeros((1, G, 3), np.float32), 'heading_class_label': np.zeros((1, G), np.int64),
+           'heading_residual_label': np.zeros((1, G), np.float32), 'size_class_label': np.zeros((1, G), np.int64),
+           'size_residual_label': np.zeros((1, G, 3), np.float32), 'sem_cls_label': np.zeros((1, G), np.int64),
+           'box_label_mask': np.zeros((1, G), np.float32), 'vote_label': np.zeros((1, N, 9), np.float32),
+           'vote_label_mask': np.zeros((1, N), np.int64), 'point_instance_labels': np.zeros((1, N), np.int64),
+           'object_instance_labels': np.zeros((1, G), np.int64)}
+    per_bin = 2 * np.pi / 12
+    shifted = (boxes[:, 6] % (2 * np.pi) + per_bin / 2) % (2 * np.pi)
+    hcls = (shifted / per_bin).astype(np.int64)
+    out['center_label'][0, :n] = boxes[:, :3]
+    out['heading_class_label'][0, :n] = hcls
+    out['heading_residual_label'][0, :n] = shifted - (hcls * per_bin + per_bin / 2)
+    out['size_class_label'][0, :n] = cls
+    out['size_residual_label'][0, :n] = boxes[:, 3:6] - mean_size_arr[cls]
+    out['sem_cls_label'][0, :n] = cls
+    out['box_label_mask'][0, :n] = 1
+    out['object_instance_labels'][0, :n] = np.arange(1, n + 1)
+    xyz = pc[:, :3].astype(np.float64)
+    for g in range(n - 1, -1, -1):                                         # the first cuboid is written last: it wins
+        c, s = np.cos(boxes[g, 6]), np.sin(boxes[g, 6])
+        R = np.array([[c, -s, 0], [s, c, 0], [0, 0, 1]])
+        local = (xyz - boxes[g, :3]) @ R
+        inside = (np.abs(local) <= boxes[g, 3:6] / 2 + margin).all(1)
+        out['vote_label'][0, inside] = np.tile(boxes[g, :3] - xyz[inside], (1, 3))
+        out['vote_label_mask'][0, inside] = 1
+        out['point_instance_labels'][0, inside] = g + 1
+    return out
