@@ -17,7 +17,7 @@ _fl = C.c_float
 _sz = C.c_size_t
 
 # name -> (restype, argtypes[, OPTIONAL]): exactly the prototypes of include/rfd_pointnet2.h / rfd_occ.h /
-# rfd_chamfer.h / rfd_eval.h / rfd_latent.h / rfd_loss.h.  OPTIONAL marks the test hooks, which a deployment build (RFD_NO_TEST_HOOKS=1, build.py)
+# rfd_chamfer.h / rfd_eval.h / rfd_latent.h / rfd_loss.h / rfd_fit.h.  OPTIONAL marks the test hooks, which a deployment build (RFD_NO_TEST_HOOKS=1, build.py)
 # leaves out.
 OPTIONAL = "optional"
 ABI = {
@@ -96,6 +96,8 @@ ABI = {
     "rfd_detection_loss_finish": (_i, [_i, _i, _i, _f, _f, _f]),
     "rfd_mask_loss_partial": (_i, [_i, _i, _f, _f, _i, _f, _f, _f, _f]),
     "rfd_mask_loss_finish": (_i, [_i, _i, _fl, _f, _f, _f]),
+    "rfd_fit_pose_run": (_i, [_i, _i, _i, _i, _i, _i, C.c_double, C.c_double, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f,
+                              _f, _f]),
     "rfd_last_error_string": (C.c_char_p, []),
     "rfd_build_arch": (C.c_char_p, []),
     "rfd_device_status": (_i, []),
@@ -108,6 +110,7 @@ ABI = {
     "rfd_gemm_packed_bytes": (_sz, [_i, _i]),
     "rfd_chain_packed_bytes_n": (_sz, [_i]),
     "rfd_head_packed_bytes": (_sz, []),
+    "rfd_fit_pose_workspace_bytes": (_sz, [_i, _i]),
 }
 SIGNATURES = {name: entry[1] for name, entry in ABI.items()}      # name -> argtypes (tests read it)
 

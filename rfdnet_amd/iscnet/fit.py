@@ -13,11 +13,24 @@ Reference quirks reproduced on purpose:
 Differences: meshes with more than 10 000 vertices are subsampled with a fixed stride (the
 reference would fail on the copy), the in-box test is an exact oriented-box test instead of a
 Delaunay hull query (identical except for points exactly on a face).
+
+method='device' (prepare_fit -> run_fit -> finish_fit) runs the same optimisation without the padding, without autograd
+and without a host round trip inside the loop: csrc/fit_pose.hip, include/rfd_fit.h.  The same quirks are kept, restated:
+  * the padded scan rows are masked in the loss, so they are simply left out; the mean's denominator stays the padded
+    count (loss_scale = 1e3 / (P * 50 000));
+  * the padded mesh rows are all the zero row, which the transform puts on the box centre; they follow the real rows, so
+    with the search's strict '<' in index order only the FIRST of them can ever be the nearest neighbour.  One extra zero
+    row after the real rows of a mesh with fewer than 10 000 of them therefore stands for all of them (a mesh with 10 000
+    rows has no padding and gets none);
+  * the nearest neighbour is piecewise constant in the parameters, so the gradient autograd builds is four sums over an
+    object's scan points (rfd_fit.h), summed in f64 in a fixed order instead of with fp32 atomics: two runs are
+    bitwise equal.
 """
 import numpy as np
 import torch
 
 from ..chamfer_distance import ChamferDistanceFunction
+from .. import _lib
 
 MAX_OBJ_POINTS = 10000          # network.py:194
 MAX_PC_IN_BOX = 50000           # network.py:195
@@ -93,12 +106,220 @@ def chamfer_loss(obj_points, pc_in_box, pc_in_box_masks, centroid_params, orient
     return torch.mean(dist2 * pc_in_box_masks) * 1e3
 
 
+METHODS = ('autograd', 'device')
+PPT_SWITCH = 65536              # scan points of all objects together: up to here fit_nn_kernel takes one point per thread
+
+
+def fit_method(fit):
+    """evaluate()'s `fit` argument -> None (no refinement) or a name of METHODS; True is 'autograd'"""
+    if fit is None or fit is False:
+        return None
+    if fit is True:
+        return 'autograd'
+    if fit not in METHODS:
+        raise ValueError("fit method %r: one of %s" % (fit, ", ".join(METHODS)))
+    return fit
+
+
+def points_in_boxes(points, corners):
+    """points (N,3), corners (K,8,3) -> bool mask (K,N): points_in_box's operations on K boxes at once."""
+    o = corners[:, 2]
+    axes = torch.stack([corners[:, 1] - corners[:, 2], corners[:, 3] - corners[:, 2], corners[:, 6] - corners[:, 2]], 1)
+    t = (points[None] - o[:, None]) @ axes.transpose(1, 2)
+    l2 = (axes * axes).sum(2)
+    return ((t >= 0) & (t <= l2[:, None])).all(dim=2)
+
+
+def normalise_mesh_points_ragged(vertices, seg, n_obj):
+    """normalise_mesh_points on the concatenated rows of n_obj meshes; seg (V) int64: the mesh of every row."""
+    v = vertices.double()
+    idx = seg[:, None].expand(-1, 3)
+
+    def extent(x):
+        hi = torch.full((n_obj, 3), -np.inf, dtype=x.dtype, device=x.device).scatter_reduce(0, idx, x, 'amax')
+        lo = torch.full((n_obj, 3), np.inf, dtype=x.dtype, device=x.device).scatter_reduce(0, idx, x, 'amin')
+        return hi, lo
+    hi, lo = extent(v)
+    v = v - ((hi + lo) / 2.)[seg]
+    v = v @ torch.tensor(TRANSFORM_SHAPENET, dtype=torch.float64, device=v.device).t()
+    hi, lo = extent(v)
+    return v / (hi - lo)[seg]
+
+
+class FitProblem(object):
+    """The ragged problem of rfd_fit_pose_run (include/rfd_fit.h) and what finish_fit needs beside it:
+    obj (n_obj,3) f32, obj_off (P+1) i32, scan (n_scan,3) f32, scan_off (P+1) i32, tile_obj / tile_start (n_tiles) i32,
+    scan_index (n_scan) i64: the row of its scene's input scan that every row of `scan` is,
+    params0 (P,4) f32, sizes (P,3) f64, corners (B,K,8,3) f64: the boxes as they came in, index_list: the (scene,
+    proposal) of every object, n_vertices / n_scan_points: per object, on the host, points_per_thread, loss_scale;
+    result: the last run_fit's.  P = 0: nothing to fit, only `corners` and `index_list` are there."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+def fit_tiles(n_scan_points, points_per_thread):
+    """per-object scan counts -> (tile_obj, tile_start) int32 arrays: an object's rows in runs of 256 * points_per_thread"""
+    step = 256 * points_per_thread
+    tile_obj, tile_start, at = [], [], 0
+    for p, n in enumerate(n_scan_points):
+        for s in range(at, at + n, step):
+            tile_obj.append(p)
+            tile_start.append(s)
+        at += n
+    return np.asarray(tile_obj, np.int32), np.asarray(tile_start, np.int32)
+
+
+def prepare_fit(meshes, proposal_ids, parsed_predictions, eval_dict, input_scan, dump_threshold, points_per_thread=None):
+    """The set-up of fit_mesh_to_scan (same arguments, same selection rules) as one ragged FitProblem on input_scan's device
+    (CPU tensors work too).  Per scene: one batched in-box test of the selected proposals, one nonzero; the vertices of
+    all objects are normalised in one concatenation.  The host waits a fixed number of times per scene, whatever the
+    number of proposals.  points_per_thread: 1 or 4 to force fit_nn_kernel's instantiation (default: by PPT_SWITCH)."""
+    dev = input_scan.device
+    as_t = lambda a, dt: (a if torch.is_tensor(a) else torch.as_tensor(np.asarray(a))).to(dev, dt)
+    corners_all = as_t(parsed_predictions['pred_corners_3d_upright_camera'], torch.float64).clone()
+    obj_prob = as_t(parsed_predictions['obj_prob'], torch.float64)
+    pred_mask = as_t(eval_dict['pred_mask'], torch.int64)
+    ids = as_t(proposal_ids, torch.int64)
+    bsize = obj_prob.shape[0]
+    scan = input_scan.double()
+    sel = ((pred_mask == 1) & (obj_prob > dump_threshold)).cpu().numpy()
+    id_rows = ids[:, :, 0].cpu().tolist()
+
+    index_list, n_scan_points, vert_list, scan_parts, row_parts, box_parts = [], [], [], [], [], []
+    for i in range(bsize):
+        js = np.nonzero(sel[i])[0]
+        if len(js) == 0:
+            continue
+        height = torch.quantile(scan[i, :, 2], 0.05)                         # np.percentile(., 5)
+        above = torch.nonzero(scan[i, :, 2] >= height)[:, 0]
+        scene_scan = scan[i, above, :3]
+        centroid, sizes, orientation = box_params_from_corners(corners_all[i, torch.as_tensor(js, device=dev)])
+        larger = flip_axis_to_depth(get_3d_box(1.2 * sizes, -orientation, flip_axis_to_camera(centroid)))
+        inside = points_in_boxes(scene_scan, larger)
+        n_in = inside.sum(1).tolist()
+        keep = [k for k, n in enumerate(n_in) if n >= 5]
+        if not keep:
+            continue
+        kt = torch.as_tensor(keep, device=dev)
+        row, col = torch.nonzero(inside[kt], as_tuple=True)                  # row-major: every object's points in scan order
+        if max(n_in[k] for k in keep) > MAX_PC_IN_BOX:
+            first = np.concatenate([[0], np.cumsum([n_in[k] for k in keep])[:-1]])
+            rank = torch.arange(row.shape[0], device=dev) - torch.as_tensor(first, device=dev)[row]
+            col = col[rank < MAX_PC_IN_BOX]
+        scan_parts.append(scene_scan[col])
+        row_parts.append(above[col])
+        box_parts.append((centroid[kt], sizes[kt], orientation[kt]))
+        for k in keep:
+            index_list.append((i, int(js[k])))
+            n_scan_points.append(min(n_in[k], MAX_PC_IN_BOX))
+            vert_list.append(meshes[id_rows[i].index(int(js[k]))].vertices)
+    if not index_list:
+        return FitProblem(P=0, corners=corners_all, index_list=[], device=dev, result=None)
+
+    P = len(index_list)
+    n_vertices = []
+    for k, verts in enumerate(vert_list):
+        verts = verts if torch.is_tensor(verts) else torch.as_tensor(np.asarray(verts))
+        if verts.shape[0] > MAX_OBJ_POINTS:
+            stride = -(-verts.shape[0] // MAX_OBJ_POINTS)
+            verts = verts[::stride]
+        vert_list[k] = verts.to(dev, torch.float64)
+        n_vertices.append(int(verts.shape[0]))
+    centroid, sizes, orientation = (torch.cat([b[c] for b in box_parts]) for c in range(3))
+    seg_host = np.repeat(np.arange(P), n_vertices)
+    seg = torch.from_numpy(seg_host).to(dev)
+    scaled = normalise_mesh_points_ragged(torch.cat(vert_list), seg, P) * sizes[seg]
+    # one zero row after every mesh that the reference would pad: it stands for all its padded rows (module docstring)
+    extra = np.asarray([v < MAX_OBJ_POINTS for v in n_vertices], np.int64)
+    obj_off = np.concatenate([[0], np.cumsum(np.asarray(n_vertices) + extra)])
+    scan_off = np.concatenate([[0], np.cumsum(n_scan_points)])
+    assert obj_off[-1] < 2 ** 31 and scan_off[-1] < 2 ** 31
+    obj = torch.zeros(int(obj_off[-1]), 3, dtype=torch.float32, device=dev)
+    dest = np.arange(len(seg_host)) + (np.cumsum(extra) - extra)[seg_host]
+    obj[torch.from_numpy(dest).to(dev)] = scaled.float()
+    return ragged_problem(obj, obj_off, torch.cat(scan_parts).float().contiguous(), scan_off,
+                          torch.cat([centroid.float(), orientation.float()[:, None]], 1).contiguous(),
+                          1e3 / (P * MAX_PC_IN_BOX), points_per_thread, corners=corners_all, index_list=index_list,
+                          n_vertices=n_vertices, sizes=sizes, scan_index=torch.cat(row_parts))
+
+
+def ragged_problem(obj, obj_off, scan, scan_off, params0, loss_scale, points_per_thread=None, **more):
+    """obj (n_obj,3), scan (n_scan,3), params0 (P,4): f32 tensors on the problem's device; obj_off, scan_off (P+1): host
+    integer arrays -> FitProblem with the tiling of points_per_thread (default: 1 up to PPT_SWITCH scan points, else 4)"""
+    dev = obj.device
+    n_scan_points = [int(n) for n in np.diff(scan_off)]
+    if points_per_thread is None:
+        points_per_thread = 1 if scan_off[-1] <= PPT_SWITCH else 4
+    tile_obj, tile_start = fit_tiles(n_scan_points, points_per_thread)
+    i32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.int32)).to(dev)
+    return FitProblem(P=len(n_scan_points), device=dev, obj=obj, obj_off=i32(obj_off), scan=scan, scan_off=i32(scan_off),
+                      n_scan_points=n_scan_points, tile_obj=i32(tile_obj), tile_start=i32(tile_start),
+                      points_per_thread=points_per_thread, params0=params0, loss_scale=loss_scale, result=None, **more)
+
+
+def run_fit(problem, lr=0.01, iterations=100, history=False):
+    """Enqueue the whole optimisation on the current stream (rfd_fit_pose_run: two launches per iteration) without waiting
+    for anything.  -> problem.result = {'params', 'best_params' (P,4), 'best_loss' (1) f32, 'best_iter' (1) i32} and with
+    history 'hist_loss' (iterations), 'hist_params' (iterations,P,4): the state before every update."""
+    if problem.P == 0:
+        return None
+    dev, P, T = problem.device, problem.P, int(iterations)
+    if dev.type != 'cuda':
+        raise ValueError("run_fit needs the problem on the GPU (prepare_fit was given CPU tensors)")
+    n_tiles = problem.tile_obj.shape[0]
+    f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+    res = {'params': problem.params0.clone(), 'best_params': f32(P, 4), 'best_loss': f32(1),
+           'best_iter': torch.empty(1, dtype=torch.int32, device=dev)}
+    if history:
+        res['hist_loss'], res['hist_params'] = f32(T), f32(T, P, 4)
+    work = torch.empty(_lib.lib().rfd_fit_pose_workspace_bytes(P, n_tiles) // 8, dtype=torch.float64, device=dev)
+    _lib.call("rfd_fit_pose_run", dev, P, problem.obj.shape[0], problem.scan.shape[0], n_tiles,
+              problem.points_per_thread, T, float(lr), float(problem.loss_scale), problem.obj.data_ptr(),
+              problem.obj_off.data_ptr(), problem.scan.data_ptr(), problem.scan_off.data_ptr(),
+              problem.tile_obj.data_ptr(), problem.tile_start.data_ptr(), res['params'].data_ptr(),
+              res['best_params'].data_ptr(), res['best_loss'].data_ptr(), res['best_iter'].data_ptr(),
+              _lib.ptr(res.get('hist_loss')), _lib.ptr(res.get('hist_params')), work.data_ptr())
+    res['workspace'] = work                                      # lives until the result is dropped
+    problem.result = res
+    return res
+
+
+def finish_fit(problem, parsed_predictions):
+    """-> parsed_predictions with the refined 'pred_corners_3d_upright_camera', 'fit_loss' and 'fit_indices' (and
+    'fit_history' = {'loss', 'params', 'best_iter'} if run_fit recorded one), as fit_mesh_to_scan returns them."""
+    out = dict(parsed_predictions)
+    corners_all = problem.corners.clone()
+    if problem.P == 0:
+        out['pred_corners_3d_upright_camera'] = corners_all
+        return out
+    res = problem.result
+    best = res['best_params'].double()
+    new_corners = get_3d_box(problem.sizes, -best[:, 3], flip_axis_to_camera(best[:, :3]))
+    where = torch.as_tensor(problem.index_list, device=problem.device)
+    corners_all[where[:, 0], where[:, 1]] = new_corners
+    out['pred_corners_3d_upright_camera'] = corners_all
+    out['fit_loss'] = float(res['best_loss'])
+    out['fit_indices'] = list(problem.index_list)
+    if 'hist_loss' in res:
+        out['fit_history'] = {'loss': res['hist_loss'], 'params': res['hist_params'], 'best_iter': int(res['best_iter'])}
+    return out
+
+
 def fit_mesh_to_scan(meshes, proposal_ids, parsed_predictions, eval_dict, input_scan, dump_threshold,
-                     lr=0.01, iterations=100):
+                     lr=0.01, iterations=100, method='autograd', history=False):
     """meshes: list of objects with `.vertices` (V,3) for proposal_ids (B,K',1) in order;
     parsed_predictions / eval_dict as returned by predictions.parse_predictions (device tensors or
     numpy); input_scan (B,N,3+) -> parsed_predictions with refined
-    'pred_corners_3d_upright_camera' (a copy; the input is not modified)."""
+    'pred_corners_3d_upright_camera' (a copy; the input is not modified).
+    method: 'autograd' (the reference's padded loop on the Chamfer kernels) or 'device' (module docstring);
+    history (method='device' only): also return 'fit_history'."""
+    if method not in METHODS:
+        raise ValueError("fit method %r: one of %s" % (method, ", ".join(METHODS)))
+    if method == 'device':
+        problem = prepare_fit(meshes, proposal_ids, parsed_predictions, eval_dict, input_scan, dump_threshold)
+        run_fit(problem, lr=lr, iterations=iterations, history=history)
+        return finish_fit(problem, parsed_predictions)
     dev = input_scan.device
     as_t = lambda a, dt: (a if torch.is_tensor(a) else torch.as_tensor(np.asarray(a))).to(dev, dt)
     corners_all = as_t(parsed_predictions['pred_corners_3d_upright_camera'], torch.float64).clone()

@@ -155,12 +155,14 @@ class ISCNet(nn.Module):
         return one_hot.view(-1, sem.size(2))
 
     @torch.no_grad()
-    def fit_mesh_to_scan(self, pred_mesh_dict, parsed_predictions, eval_dict, input_scan, dump_threshold):
+    def fit_mesh_to_scan(self, pred_mesh_dict, parsed_predictions, eval_dict, input_scan, dump_threshold,
+                         method='autograd'):
         """Box refinement of the evaluation path (network.py:182-303); see iscnet/fit.py.
-        pred_mesh_dict = {'meshes': [...], 'proposal_ids': (B,K',1)} as in the reference."""
+        pred_mesh_dict = {'meshes': [...], 'proposal_ids': (B,K',1)} as in the reference.
+        method: 'autograd' (the reference's padded loop) or 'device' (the ragged loop of csrc/fit_pose.hip)."""
         from . import fit
         return fit.fit_mesh_to_scan(pred_mesh_dict['meshes'], pred_mesh_dict['proposal_ids'], parsed_predictions,
-                                    eval_dict, input_scan, dump_threshold)
+                                    eval_dict, input_scan, dump_threshold, method=method)
 
     def generate(self, data, selection='all', return_grids=False, hook=None):
         """data['point_clouds'] (B,N,3+f) -> (end_points, proposal ids, meshes).  hook: see reconstruct()."""
@@ -211,7 +213,8 @@ class ISCNet(nn.Module):
     def evaluate(self, data, fit=True, ap_iou_thresh=(0.25, 0.5), timing=False, completion=False, completion_eps=None,
                  losses=False):
         """The tail of the reference's `generate` in test mode (network.py:85-177): detection and completion with
-        selection='nms', then (fit) the box refinement of fit_mesh_to_scan, then the evaluation records of the --
+        selection='nms', then (fit: True or 'autograd', or 'device' for the ragged loop of csrc/fit_pose.hip; False for
+        none) the box refinement of fit_mesh_to_scan, then the evaluation records of the --
         refined -- boxes against the ground-truth labels in `data` (center_label, heading_class_label,
         heading_residual_label, size_class_label, size_residual_label, sem_cls_label, box_label_mask).
         -> (end_points, proposal ids, meshes, records): what generate returns plus evaluation.SceneRecords, queued on
@@ -227,7 +230,8 @@ class ISCNet(nn.Module):
         carries vote_label (B,N,9) and vote_label_mask (B,N), and for the mask loss point_instance_labels (B,N) and
         object_instance_labels (B,G) (absent: mask loss 0).  end_points['loss'] = ISCNet.loss(...): DetectionLoss's thirteen
         keys, completion_loss, mask_loss, and `total` with ONet_Loss's weight * (completion + 100 mask) added."""
-        from . import evaluation
+        from . import evaluation, fit as fit_module
+        method = fit_module.fit_method(fit)
         captured = {}
         hook = (lambda codes, cls: captured.update(codes=codes, cls=cls)) if completion else None
         if losses:
@@ -244,9 +248,10 @@ class ISCNet(nn.Module):
             end_points['loss'] = self.loss((end_points, value), data)
         parsed = end_points['parsed_predictions']
         eval_dict = {'pred_mask': end_points['pred_mask']}
-        if fit and len(meshes):
+        if method and len(meshes):
             parsed = self.fit_mesh_to_scan({'meshes': meshes, 'proposal_ids': ids}, parsed, eval_dict,
-                                           data['point_clouds'], self.cfg.config['generation']['dump_threshold'])
+                                           data['point_clouds'], self.cfg.config['generation']['dump_threshold'],
+                                           method=method)
             end_points['parsed_predictions'] = parsed
         parsed_gts = evaluation.parse_groundtruths(data, self.cfg.dataset_config)
         records = evaluation.scene_records(eval_dict, parsed, parsed_gts, getattr(self.cfg, 'eval_overrides', None),

@@ -1,6 +1,6 @@
 """Detection mAP / AR of a sweep through ISCNet.evaluate, with the cost of the evaluation stage.
 
-    python tools/eval_sweep.py --scenes 8 [--gpus M] [--no-fit]
+    python tools/eval_sweep.py --scenes 8 [--gpus M] [--no-fit | --fit-method device]
     python tools/eval_sweep.py --weight ckpt.pth --gt DIR --mean_size_npz scannet_means.npz
 
 Synthetic scenes (rfdnet_amd.synthetic.synthetic_scene(return_boxes=True): the 12 furniture cuboids are the ground
@@ -89,6 +89,8 @@ def main():
     ap.add_argument("--resolution_0", type=int, default=None)
     ap.add_argument("--upsampling_steps", type=int, default=None)
     ap.add_argument("--no-fit", action="store_true", help="score the decoded boxes without fit_mesh_to_scan")
+    ap.add_argument("--fit-method", choices=("autograd", "device"), default="autograd",
+                    help="fit_mesh_to_scan's method: the padded autograd loop (default) or the ragged loop on the device")
     ap.add_argument("--completion", action="store_true",
                     help="synthetic scenes, --gpus 1: also report the completion loss and the voxel IoU")
     ap.add_argument("--out", type=str, default=os.path.join(ROOT, "profiles", "eval_stage.json"))
@@ -126,7 +128,7 @@ def main():
     files = sorted(glob.glob(os.path.join(args.gt, "*.npz"))) if args.gt else None
     n_scenes = len(files) if files else args.scenes
     mine = sharding.scene_ids_for_rank(n_scenes, rank, world)
-    fit = not args.no_fit
+    fit = False if args.no_fit else args.fit_method                      # evaluate()'s `fit`: a method name or False
     thr = (0.25, 0.5)
     dump = cfg.config['generation']['dump_threshold']
 
@@ -136,7 +138,7 @@ def main():
         end_points, ids, meshes = net.generate(data, selection='nms')
         if fit and len(meshes):
             net.fit_mesh_to_scan({'meshes': meshes, 'proposal_ids': ids}, end_points['parsed_predictions'],
-                                 {'pred_mask': end_points['pred_mask']}, data['point_clouds'], dump)
+                                 {'pred_mask': end_points['pred_mask']}, data['point_clouds'], dump, method=fit)
 
     def timed(fn, data):
         torch.cuda.synchronize()
@@ -189,7 +191,7 @@ def main():
         steps = times[:, 0].sum()
         rate = lambda col: float(steps / times[:, col].max()) if steps else None
         line = {"tool": "eval_sweep", "weights": "checkpoint" if args.weight else "seeded", "scenes": int(steps),
-                "gpus": world, "fit": fit, "points": args.points if not files else None,
+                "gpus": world, "fit": bool(fit), "fit_method": fit or None, "points": args.points if not files else None,
                 "scenes_in_flight": 1,        # one scene at a time per GPU, timed between device synchronisations
                 "mAP@0.25": num(m25)['mAP'], "AR@0.25": num(m25)['AR'], "mAP@0.5": num(m50)['mAP'],
                 "AR@0.5": num(m50)['AR'], "per_class@0.25": num(m25), "per_class@0.5": num(m50),
