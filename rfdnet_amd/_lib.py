@@ -234,6 +234,23 @@ def ptr(t):
     return None if t is None else t.data_ptr()
 
 
+def rows(t):
+    """(K,T) tensor -> (t', ld): the rows as a kernel reads them, `ld` elements apart.  A row-strided view (unit stride
+    along T, rows that do not overlap) is read in place, anything else through a contiguous copy; one row, or one
+    column, has no stride to respect."""
+    K, T = t.shape
+    if (T > 1 and t.stride(1) != 1) or (K > 1 and t.stride(0) < T):
+        t = t.contiguous()
+    return t, int(t.stride(0)) if K > 1 else T
+
+
+def as_tensor(a, device, dtype):
+    """numpy (or anything numpy converts) or a tensor -> a tensor on `device` of `dtype`; no copy when it already is"""
+    import numpy as np
+    import torch
+    return (a if torch.is_tensor(a) else torch.as_tensor(np.asarray(a))).to(device, dtype)
+
+
 def call(name, device, *args):
     """The one way a host module launches: ABI entry `name` (one whose last C parameter is the stream) with `args` and
     the current stream of `device`, on that device; a non-zero return raises, naming `name`."""

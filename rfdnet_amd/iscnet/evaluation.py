@@ -23,7 +23,7 @@ import numpy as np
 import torch
 
 from .. import _lib
-from . import predictions
+from . import box_util, predictions
 
 MAX_THRESHOLDS = 4
 LIST_GROUPS = 16384          # (scene, class) groups per launch pair of records_from_lists
@@ -41,13 +41,10 @@ def parse_groundtruths(gt_data, dataset_config):
     """Ground-truth labels -> {'sem_cls_label' (B,G), 'gt_corners_3d_upright_camera' (B,G,8,3) f64,
     'box_label_mask' (B,G)}, device tensors; rows with box_label_mask == 0 are zero."""
     center = gt_data['center_label'][:, :, 0:3].double()
-    nh = dataset_config.num_heading_bin
-    # class2angle / class2size (scannet_config.py:43-53, :71-73) in double, as the reference's numpy scalars
-    angle = gt_data['heading_class_label'].double() * (2 * np.pi / float(nh)) + gt_data['heading_residual_label'].double()
-    angle = torch.where(angle > np.pi, angle - 2 * np.pi, angle)
-    mean_size = torch.from_numpy(np.asarray(dataset_config.mean_size_arr, dtype=np.float64)).to(center.device)
-    size = mean_size[gt_data['size_class_label'].long()] + gt_data['size_residual_label'].double()
-    corners = predictions.box_corners_upright_camera(center, size, angle)
+    angle = box_util.class2angle(gt_data['heading_class_label'], gt_data['heading_residual_label'],
+                                 dataset_config.num_heading_bin)
+    size = box_util.class2size(gt_data['size_class_label'], gt_data['size_residual_label'], dataset_config.mean_size_arr)
+    corners = box_util.box_corners_upright_camera(center, size, angle)
     mask = gt_data['box_label_mask']
     corners = corners * (mask != 0).view(*mask.shape, 1, 1).to(corners.dtype)
     return {'sem_cls_label': gt_data['sem_cls_label'], 'gt_corners_3d_upright_camera': corners,
@@ -156,12 +153,11 @@ def scene_records(eval_dict, parsed_predictions, parsed_gts, config=None, ap_iou
     thr = _thresholds(ap_iou_thresh)
     corners = parsed_predictions['pred_corners_3d_upright_camera']
     dev = corners.device if torch.is_tensor(corners) and corners.is_cuda else torch.device('cuda', torch.cuda.current_device())
-    as_t = lambda a, dt: (a if torch.is_tensor(a) else torch.as_tensor(np.asarray(a))).to(dev, dt)
-    corners = as_t(corners, torch.float64)
-    obj_prob = as_t(parsed_predictions['obj_prob'], torch.float32)
-    sem = as_t(parsed_predictions['sem_cls_probs'], torch.float32)
-    pred_cls = as_t(parsed_predictions['pred_sem_cls'], torch.int64)
-    mask = as_t(eval_dict['pred_mask'], torch.int64)
+    corners = _lib.as_tensor(corners, dev, torch.float64)
+    obj_prob = _lib.as_tensor(parsed_predictions['obj_prob'], dev, torch.float32)
+    sem = _lib.as_tensor(parsed_predictions['sem_cls_probs'], dev, torch.float32)
+    pred_cls = _lib.as_tensor(parsed_predictions['pred_sem_cls'], dev, torch.int64)
+    mask = _lib.as_tensor(eval_dict['pred_mask'], dev, torch.int64)
     B, K, C = sem.shape
     take = (mask == 1) & (obj_prob > cfg['conf_thresh'])
     if cfg['per_class_proposal']:
@@ -170,9 +166,9 @@ def scene_records(eval_dict, parsed_predictions, parsed_gts, config=None, ap_iou
     else:
         score = obj_prob.unsqueeze(1).expand(B, C, K).contiguous()
         valid = take.unsqueeze(1) & (pred_cls.unsqueeze(1) == torch.arange(C, device=dev).view(1, C, 1))
-    gt_corners = as_t(parsed_gts['gt_corners_3d_upright_camera'], torch.float64)
-    gt_cls = as_t(parsed_gts['sem_cls_label'], torch.int32).contiguous()
-    gt_valid = (as_t(parsed_gts['box_label_mask'], torch.float32) == 1).to(torch.uint8).contiguous()
+    gt_corners = _lib.as_tensor(parsed_gts['gt_corners_3d_upright_camera'], dev, torch.float64)
+    gt_cls = _lib.as_tensor(parsed_gts['sem_cls_label'], dev, torch.int32).contiguous()
+    gt_valid = (_lib.as_tensor(parsed_gts['box_label_mask'], dev, torch.float32) == 1).to(torch.uint8).contiguous()
     return _records(corners, score, valid.to(torch.uint8).contiguous(), gt_corners, gt_cls, gt_valid, thr, timing)
 
 
@@ -397,15 +393,13 @@ def voxel_iou(logits, logit_threshold, gt_voxels, return_counts=False):
     if not logits.is_cuda:
         raise RuntimeError("CPU not supported")
     K = logits.shape[0]
-    logits = logits.reshape(K, -1).float()
-    if logits.stride(-1) != 1 or (K > 1 and logits.stride(0) < logits.shape[1]):
-        logits = logits.contiguous()
+    logits, ld = _lib.rows(logits.reshape(K, -1).float())
     V = logits.shape[1]
     gt = gt_voxels.to(logits.device).reshape(K, -1).float().contiguous()
     assert gt.shape == (K, V)
     inter = torch.empty(K, dtype=torch.int32, device=logits.device)
     union = torch.empty(K, dtype=torch.int32, device=logits.device)
-    _lib.call("rfd_voxel_iou", logits.device, K, V, logits.data_ptr(), int(logits.stride(0)) if K > 1 else V,
+    _lib.call("rfd_voxel_iou", logits.device, K, V, logits.data_ptr(), ld,
               float(logit_threshold), gt.data_ptr(), inter.data_ptr(), union.data_ptr())
     iou = inter.float() / union.float()
     return (iou, inter, union) if return_counts else iou

@@ -1,8 +1,15 @@
 """fit_mesh_to_scan: refine the centre and heading of every detected box so that its generated
 mesh lies on the scan points inside the (enlarged) box -- 100 Adam steps on a one-sided Chamfer
-loss (models/iscnet/modules/network.py:182-303).  Everything stays on the device: the
-nearest-neighbour searches and their gradients are the HIP kernels of csrc/chamfer.hip
-(rfdnet_amd.chamfer_distance), the box bookkeeping is batched tensor code.
+loss (models/iscnet/modules/network.py:182-303).  Everything stays on the device.
+
+One set-up, two optimisers.  prepare_fit selects the proposals, cuts the scan at the 5th height percentile, tests the
+points against the box at 1.2x its size, and normalises and scales the meshes, for all objects at once, into one ragged
+FitProblem; finish_fit writes the best parameters back as corners.  Between them:
+  method='autograd'   run_fit_autograd: padded_problem pads the ragged rows to the reference's 10 000 / 50 000 and Adam
+                      runs on chamfer_loss, whose searches and gradients are the kernels of csrc/chamfer.hip
+                      (rfdnet_amd.chamfer_distance); the gradient is summed with fp32 atomics;
+  method='device'     run_fit: the same optimisation without the padding, without autograd and without a host round
+                      trip inside the loop (csrc/fit_pose.hip, include/rfd_fit.h).
 
 Reference quirks reproduced on purpose:
   * mesh points and scan points are zero-padded to 10 000 / 50 000 rows and the PADDED mesh
@@ -14,64 +21,33 @@ Differences: meshes with more than 10 000 vertices are subsampled with a fixed s
 reference would fail on the copy), the in-box test is an exact oriented-box test instead of a
 Delaunay hull query (identical except for points exactly on a face).
 
-method='device' (prepare_fit -> run_fit -> finish_fit) runs the same optimisation without the padding, without autograd
-and without a host round trip inside the loop: csrc/fit_pose.hip, include/rfd_fit.h.  The same quirks are kept, restated:
+The ragged problem keeps the same quirks, restated:
   * the padded scan rows are masked in the loss, so they are simply left out; the mean's denominator stays the padded
     count (loss_scale = 1e3 / (P * 50 000));
   * the padded mesh rows are all the zero row, which the transform puts on the box centre; they follow the real rows, so
     with the search's strict '<' in index order only the FIRST of them can ever be the nearest neighbour.  One extra zero
     row after the real rows of a mesh with fewer than 10 000 of them therefore stands for all of them (a mesh with 10 000
-    rows has no padding and gets none);
+    rows has no padding and gets none; padded_problem leaves that row out and pads with zeros again);
   * the nearest neighbour is piecewise constant in the parameters, so the gradient autograd builds is four sums over an
     object's scan points (rfd_fit.h), summed in f64 in a fixed order instead of with fp32 atomics: two runs are
     bitwise equal.
+
+The two methods share their set-up, so their agreement says nothing about it.  What checks the set-up is independent of
+prepare_fit: the per-object loop `per_object_setup` of tests/test_fit_device_cpu.py, built from the single-object forms
+points_in_box and normalise_mesh_points below and compared with prepare_fit (and padded_problem) bit for bit, and the
+fixture F_FIT, which is the reference's own function's run.  Keep that loop a loop: calling prepare_fit from it would
+compare the batched code with itself.
 """
 import numpy as np
 import torch
 
 from ..chamfer_distance import ChamferDistanceFunction
 from .. import _lib
+from .box_util import box_params_from_corners, flip_axis_to_camera, flip_axis_to_depth, get_3d_box  # noqa: F401
 
 MAX_OBJ_POINTS = 10000          # network.py:194
 MAX_PC_IN_BOX = 50000           # network.py:195
 TRANSFORM_SHAPENET = ((0., 0., -1.), (-1., 0., 0.), (0., 1., 0.))      # network.py:191
-
-
-def flip_axis_to_depth(p):
-    """cam (x, y, z) -> depth (x, z, -y)  (net_utils/libs.py:116-120)."""
-    return torch.stack([p[..., 0], p[..., 2], -p[..., 1]], -1)
-
-
-def flip_axis_to_camera(p):
-    """depth (x, y, z) -> cam (x, -z, y)  (net_utils/libs.py:98-105)."""
-    return torch.stack([p[..., 0], -p[..., 2], p[..., 1]], -1)
-
-
-def get_3d_box(size, heading, center):
-    """size (...,3) [l,w,h], heading (...), center (...,3) -> corners (...,8,3)
-    (net_utils/box_util.py:183-198; roty(t) = [[c,0,s],[0,1,0],[-s,0,c]])."""
-    dt, dev = size.dtype, size.device
-    sx = torch.tensor([1, 1, -1, -1, 1, 1, -1, -1], dtype=dt, device=dev)
-    sy = torch.tensor([1, 1, 1, 1, -1, -1, -1, -1], dtype=dt, device=dev)
-    sz = torch.tensor([1, -1, -1, 1, 1, -1, -1, 1], dtype=dt, device=dev)
-    xc = size[..., 0:1] / 2 * sx
-    yc = size[..., 2:3] / 2 * sy
-    zc = size[..., 1:2] / 2 * sz
-    c, s = torch.cos(heading).unsqueeze(-1), torch.sin(heading).unsqueeze(-1)
-    x = c * xc + s * zc
-    z = -s * xc + c * zc
-    return torch.stack([x + center[..., 0:1], yc + center[..., 1:2], z + center[..., 2:3]], -1)
-
-
-def box_params_from_corners(corners_cam):
-    """(P,8,3) upright-camera corners -> centroid (P,3), sizes (P,3), orientation (P), depth
-    frame (network.py:220-229)."""
-    d = flip_axis_to_depth(corners_cam)
-    centroid = (d.max(dim=1)[0] + d.min(dim=1)[0]) / 2.
-    fwd, left, up = d[:, 1] - d[:, 2], d[:, 0] - d[:, 1], d[:, 6] - d[:, 2]
-    orientation = torch.atan2(fwd[:, 1], fwd[:, 0])
-    sizes = torch.stack([fwd.norm(dim=1), left.norm(dim=1), up.norm(dim=1)], 1)
-    return centroid, sizes, orientation
 
 
 def points_in_box(points, corners):
@@ -176,11 +152,10 @@ def prepare_fit(meshes, proposal_ids, parsed_predictions, eval_dict, input_scan,
     all objects are normalised in one concatenation.  The host waits a fixed number of times per scene, whatever the
     number of proposals.  points_per_thread: 1 or 4 to force fit_nn_kernel's instantiation (default: by PPT_SWITCH)."""
     dev = input_scan.device
-    as_t = lambda a, dt: (a if torch.is_tensor(a) else torch.as_tensor(np.asarray(a))).to(dev, dt)
-    corners_all = as_t(parsed_predictions['pred_corners_3d_upright_camera'], torch.float64).clone()
-    obj_prob = as_t(parsed_predictions['obj_prob'], torch.float64)
-    pred_mask = as_t(eval_dict['pred_mask'], torch.int64)
-    ids = as_t(proposal_ids, torch.int64)
+    corners_all = _lib.as_tensor(parsed_predictions['pred_corners_3d_upright_camera'], dev, torch.float64).clone()
+    obj_prob = _lib.as_tensor(parsed_predictions['obj_prob'], dev, torch.float64)
+    pred_mask = _lib.as_tensor(eval_dict['pred_mask'], dev, torch.int64)
+    ids = _lib.as_tensor(proposal_ids, dev, torch.int64)
     bsize = obj_prob.shape[0]
     scan = input_scan.double()
     sel = ((pred_mask == 1) & (obj_prob > dump_threshold)).cpu().numpy()
@@ -306,6 +281,49 @@ def finish_fit(problem, parsed_predictions):
     return out
 
 
+def padded_problem(problem):
+    """The ragged problem in the reference's shapes (network.py:194-195, :246-269) -> obj_points (P,10000,3),
+    pc_in_box (P,50000,3), pc_masks (P,50000): 1 on the real scan rows, centroid_params (P,3), orientation_params (P),
+    all f32.  Only an object's real mesh rows are copied: the stand-in zero row is left to the padding."""
+    P, dev = problem.P, problem.device
+    obj_off, scan_off = problem.obj_off.tolist(), problem.scan_off.tolist()
+    obj_points = torch.zeros(P, MAX_OBJ_POINTS, 3, dtype=torch.float32, device=dev)
+    pc_in_box = torch.zeros(P, MAX_PC_IN_BOX, 3, dtype=torch.float32, device=dev)
+    pc_masks = torch.zeros(P, MAX_PC_IN_BOX, dtype=torch.float32, device=dev)
+    for p in range(P):
+        V, S = problem.n_vertices[p], problem.n_scan_points[p]
+        obj_points[p, :V] = problem.obj[obj_off[p]:obj_off[p] + V]
+        pc_in_box[p, :S] = problem.scan[scan_off[p]:scan_off[p] + S]
+        pc_masks[p, :S] = 1
+    fresh = dict(memory_format=torch.contiguous_format)          # tensors of their own: the optimiser updates in place
+    return obj_points, pc_in_box, pc_masks, problem.params0[:, :3].clone(**fresh), problem.params0[:, 3].clone(**fresh)
+
+
+def run_fit_autograd(problem, lr=0.01, iterations=100):
+    """The reference's loop (network.py:271-291) on the padded problem: Adam on chamfer_loss, whose gradient autograd
+    builds from the Chamfer kernels (fp32 atomics: not run-to-run deterministic).  -> problem.result = {'best_params'
+    (P,4) f32, 'best_loss'}: the state BEFORE the update of the iteration with the lowest loss."""
+    if problem.P == 0:
+        return None
+    obj_points, pc_in_box, pc_masks, centroid_params, orientation_params = padded_problem(problem)
+    centroid_params.requires_grad_(True)
+    orientation_params.requires_grad_(True)
+    optimizer = torch.optim.Adam([centroid_params, orientation_params], lr=lr)
+    res = {'best_params': problem.params0.clone(), 'best_loss': 1e6}
+    with torch.enable_grad():
+        for _ in range(iterations):
+            optimizer.zero_grad()
+            loss = chamfer_loss(obj_points, pc_in_box, pc_masks, centroid_params, orientation_params)
+            cur = float(loss.detach())
+            if cur < res['best_loss']:
+                res['best_params'] = torch.cat([centroid_params.detach(), orientation_params.detach()[:, None]], 1)
+                res['best_loss'] = cur
+            loss.backward()
+            optimizer.step()
+    problem.result = res
+    return res
+
+
 def fit_mesh_to_scan(meshes, proposal_ids, parsed_predictions, eval_dict, input_scan, dump_threshold,
                      lr=0.01, iterations=100, method='autograd', history=False):
     """meshes: list of objects with `.vertices` (V,3) for proposal_ids (B,K',1) in order;
@@ -316,80 +334,9 @@ def fit_mesh_to_scan(meshes, proposal_ids, parsed_predictions, eval_dict, input_
     history (method='device' only): also return 'fit_history'."""
     if method not in METHODS:
         raise ValueError("fit method %r: one of %s" % (method, ", ".join(METHODS)))
+    problem = prepare_fit(meshes, proposal_ids, parsed_predictions, eval_dict, input_scan, dump_threshold)
     if method == 'device':
-        problem = prepare_fit(meshes, proposal_ids, parsed_predictions, eval_dict, input_scan, dump_threshold)
         run_fit(problem, lr=lr, iterations=iterations, history=history)
-        return finish_fit(problem, parsed_predictions)
-    dev = input_scan.device
-    as_t = lambda a, dt: (a if torch.is_tensor(a) else torch.as_tensor(np.asarray(a))).to(dev, dt)
-    corners_all = as_t(parsed_predictions['pred_corners_3d_upright_camera'], torch.float64).clone()
-    obj_prob = as_t(parsed_predictions['obj_prob'], torch.float64)
-    pred_mask = as_t(eval_dict['pred_mask'], torch.int64)
-    ids = as_t(proposal_ids, torch.int64)
-    bsize, n_prop = obj_prob.shape
-    scan = input_scan.double()
-
-    index_list, obj_list, pc_list, mask_list, corner_list = [], [], [], [], []
-    sel = ((pred_mask == 1) & (obj_prob > dump_threshold)).cpu().numpy()
-    for i in range(bsize):
-        id_row = ids[i, :, 0].tolist()
-        height = torch.quantile(scan[i, :, 2], 0.05)                         # np.percentile(., 5)
-        scene_scan = scan[i, scan[i, :, 2] >= height, :3]
-        for j in range(n_prop):
-            if not sel[i, j]:
-                continue
-            verts = meshes[id_row.index(j)].vertices
-            verts = verts if torch.is_tensor(verts) else torch.as_tensor(np.asarray(verts))
-            verts = verts.to(dev)
-            if verts.shape[0] > MAX_OBJ_POINTS:
-                stride = -(-verts.shape[0] // MAX_OBJ_POINTS)
-                verts = verts[::stride]
-            obj_points = normalise_mesh_points(verts)
-            centroid, sizes, orientation = box_params_from_corners(corners_all[i, j][None])
-            larger = flip_axis_to_depth(get_3d_box(1.2 * sizes, -orientation, flip_axis_to_camera(centroid)))[0]
-            inside = scene_scan[points_in_box(scene_scan, larger)]
-            if inside.shape[0] < 5:
-                continue
-            inside = inside[:MAX_PC_IN_BOX]
-            om = torch.zeros(MAX_OBJ_POINTS, 3, dtype=torch.float64, device=dev)
-            om[:obj_points.shape[0]] = obj_points
-            pm = torch.zeros(MAX_PC_IN_BOX, 3, dtype=torch.float64, device=dev)
-            pm[:inside.shape[0]] = inside
-            mk = torch.zeros(MAX_PC_IN_BOX, dtype=torch.float32, device=dev)
-            mk[:inside.shape[0]] = 1
-            index_list.append((i, j))
-            obj_list.append(om * sizes)                                       # scale to the predicted sizes
-            pc_list.append(pm)
-            mask_list.append(mk)
-            corner_list.append((centroid[0], sizes[0], orientation[0]))
-    out = dict(parsed_predictions)
-    if not index_list:
-        out['pred_corners_3d_upright_camera'] = corners_all
-        return out
-
-    obj_points = torch.stack(obj_list).float()
-    pc_in_box = torch.stack(pc_list).float()
-    pc_masks = torch.stack(mask_list)
-    sizes = torch.stack([c[1] for c in corner_list])
-    centroid_params = torch.stack([c[0] for c in corner_list]).float().requires_grad_(True)
-    orientation_params = torch.stack([c[2] for c in corner_list]).float().requires_grad_(True)
-    optimizer = torch.optim.Adam([centroid_params, orientation_params], lr=lr)
-    best_c, best_o, best_loss = None, None, 1e6
-    with torch.enable_grad():
-        for _ in range(iterations):
-            optimizer.zero_grad()
-            loss = chamfer_loss(obj_points, pc_in_box, pc_masks, centroid_params, orientation_params)
-            cur = float(loss.detach())
-            if cur < best_loss:
-                best_c = centroid_params.detach().clone()
-                best_o = orientation_params.detach().clone()
-                best_loss = cur
-            loss.backward()
-            optimizer.step()
-    new_corners = get_3d_box(sizes, -best_o.double(), flip_axis_to_camera(best_c.double()))
-    for k, (i, j) in enumerate(index_list):
-        corners_all[i, j] = new_corners[k]
-    out['pred_corners_3d_upright_camera'] = corners_all
-    out['fit_loss'] = best_loss
-    out['fit_indices'] = index_list
-    return out
+    else:
+        run_fit_autograd(problem, lr=lr, iterations=iterations)
+    return finish_fit(problem, parsed_predictions)

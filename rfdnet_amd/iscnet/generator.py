@@ -18,7 +18,7 @@ import numpy as np
 import torch
 
 from .. import _lib
-from .occ_decoder import MODE_F16X3, TILE, run_with_range_fallback
+from .occ_decoder import MODE_F16X3, TILE, logit_threshold, run_with_range_fallback
 
 
 class Mesh(object):
@@ -129,7 +129,7 @@ class Generator3D(object):
 
     # ---- batched implementation --------------------------------------------------
     def logit_threshold(self):
-        return float(np.log(self.threshold) - np.log(1. - self.threshold))   # generator.py:85
+        return logit_threshold(self.threshold)
 
     def generate_grids(self, object_features, cls_codes=None, fold_out=None):
         """-> value grids (K, n, n, n) float32 on the device; n = resolution0 for

@@ -42,7 +42,7 @@ def _need_cuda(t):
 
 def _as(t, dtype, dev):
     """`t` on `dev`, contiguous, of `dtype`: no kernel when it already is (the dataloader's dtypes)"""
-    return t.to(device=dev, dtype=dtype).contiguous()
+    return _lib.as_tensor(t, dev, dtype).contiguous()
 
 
 def _strided(t):

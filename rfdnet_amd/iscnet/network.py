@@ -164,8 +164,11 @@ class ISCNet(nn.Module):
         return fit.fit_mesh_to_scan(pred_mesh_dict['meshes'], pred_mesh_dict['proposal_ids'], parsed_predictions,
                                     eval_dict, input_scan, dump_threshold, method=method)
 
-    def generate(self, data, selection='all', return_grids=False, hook=None):
-        """data['point_clouds'] (B,N,3+f) -> (end_points, proposal ids, meshes).  hook: see reconstruct()."""
+    def generate(self, data, selection='all', return_grids=False, hook=None, labels_sink=None):
+        """data['point_clouds'] (B,N,3+f) -> (end_points, proposal ids, meshes).  hook: see reconstruct().
+        labels_sink: a dictionary, for the test mode with losses: `data` then carries the ground truth, and the proposal ->
+        ground-truth pairing is made BEFORE skip propagation, so that the proposals' instance labels exist when the codes
+        are built (network.py:97, 123-124); the sink receives 'pairs' (evaluation.proposal_to_gt) and 'mask_loss'."""
         pc = data['point_clouds']
         end_points, proposal_features = self.detect(pc)
         ids = self.select_proposals(end_points, selection, pc)
@@ -175,7 +178,15 @@ class ISCNet(nn.Module):
             from .. import _lib
             _lib.raise_status(_lib.stream_status_bits())
             return end_points, ids, []
-        out = self.reconstruct(end_points, proposal_features, ids, pc, return_grids=return_grids, hook=hook)
+        labels = None
+        if labels_sink is not None:
+            from . import evaluation
+            labels_sink['pairs'] = pairs = evaluation.proposal_to_gt(end_points, data, ids)
+            if self.cfg.config['data']['skip_propagate'] and 'point_instance_labels' in data and \
+                    'object_instance_labels' in data:
+                wanted = torch.gather(data['object_instance_labels'].to(pc.device), 1, pairs[:, :, 1])
+                labels = (data['point_instance_labels'], wanted, labels_sink)
+        out = self.reconstruct(end_points, proposal_features, ids, pc, return_grids=return_grids, hook=hook, labels=labels)
         return end_points, ids, out
 
     def loss(self, est_data, gt_data):
@@ -189,26 +200,6 @@ class ISCNet(nn.Module):
                           'mask_loss': completion_loss['mask_loss']}
             total_loss['total'] = total_loss['total'] + completion_loss['total_loss']
         return total_loss
-
-    def _generate_with_labels(self, data, hook, sink):
-        """generate(selection='nms') of the test mode with losses: the proposal -> ground-truth pairing is made BEFORE skip
-        propagation, so the proposals' instance labels exist when the codes are built (network.py:97, 123-124)."""
-        from . import evaluation
-        from .. import _lib
-        pc = data['point_clouds']
-        end_points, proposal_features = self.detect(pc)
-        ids = self.select_proposals(end_points, 'nms', pc)
-        if ids.shape[1] == 0:
-            _lib.raise_status(_lib.stream_status_bits())
-            return end_points, ids, []
-        sink['pairs'] = pairs = evaluation.proposal_to_gt(end_points, data, ids)
-        labels = None
-        if self.cfg.config['data']['skip_propagate'] and 'point_instance_labels' in data and \
-                'object_instance_labels' in data:
-            wanted = torch.gather(data['object_instance_labels'].to(pc.device), 1, pairs[:, :, 1])
-            labels = (data['point_instance_labels'], wanted, sink)
-        out = self.reconstruct(end_points, proposal_features, ids, pc, hook=hook, labels=labels)
-        return end_points, ids, out
 
     def evaluate(self, data, fit=True, ap_iou_thresh=(0.25, 0.5), timing=False, completion=False, completion_eps=None,
                  losses=False):
@@ -234,10 +225,7 @@ class ISCNet(nn.Module):
         method = fit_module.fit_method(fit)
         captured = {}
         hook = (lambda codes, cls: captured.update(codes=codes, cls=cls)) if completion else None
-        if losses:
-            end_points, ids, meshes = self._generate_with_labels(data, hook, captured)
-        else:
-            end_points, ids, meshes = self.generate(data, selection='nms', hook=hook)
+        end_points, ids, meshes = self.generate(data, selection='nms', hook=hook, labels_sink=captured if losses else None)
         if completion:
             self._completion_block(end_points, data, ids, captured, completion_eps)
         if losses:

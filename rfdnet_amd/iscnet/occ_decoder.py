@@ -14,6 +14,7 @@ fc_out.{weight(1,256,1),bias}.
 import ctypes as C
 import os
 
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -22,6 +23,11 @@ from .. import _lib, occ_fold
 MODE_F16X3 = 3   # parity mode (fp32-class logits)
 MODE_F16X1 = 1   # throughput mode
 TILE = 128
+
+
+def logit_threshold(threshold):
+    """probs >= threshold as a comparison of logits (generator.py:85)"""
+    return float(np.log(threshold) - np.log(1. - threshold))
 
 
 def run_with_range_fallback(dec, run, device, before=None):

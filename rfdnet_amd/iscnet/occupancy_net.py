@@ -2,13 +2,12 @@
 attribute name (`decoder` => state_dict keys completion.decoder.*), the prior over z, the mesh generator and -- once
 enable_latent_encoder() is called -- the latent encoder q(z | p, occ, c) with the completion loss of the test mode
 (compute_loss: KL + BCE + the 16^3 voxel example)."""
-import numpy as np
 import torch
 import torch.distributions as dist
 import torch.nn as nn
 
 from .generator import Generator3D
-from .occ_decoder import DecoderCBatchNorm
+from .occ_decoder import DecoderCBatchNorm, logit_threshold
 from .registers import MODULES
 
 
@@ -76,8 +75,7 @@ class ONet(nn.Module):
         return torch.stack(torch.meshgrid(lin, lin, lin, indexing='ij'), dim=-1).view(-1, 3).to(device)
 
     def logit_threshold(self):
-        """probs >= threshold as a comparison of logits (Generator3D.logit_threshold's conversion)"""
-        return float(np.log(self.threshold) - np.log(1. - self.threshold))
+        return logit_threshold(self.threshold)
 
     @torch.no_grad()
     def compute_loss(self, input_features_for_completion, input_points_for_completion,
@@ -160,15 +158,8 @@ def bce_logits_rowsum(logits, target):
         raise RuntimeError("CPU not supported")
     K, T = logits.shape
     assert target.shape == (K, T) and logits.dtype == torch.float32 and target.dtype == torch.float32
-    if T > 1 and logits.stride(1) != 1:
-        logits = logits.contiguous()
-    if T > 1 and target.stride(1) != 1:
-        target = target.contiguous()
-    ld_l = logits.stride(0) if K > 1 else T
-    ld_t = target.stride(0) if K > 1 else T
-    if ld_l < T or ld_t < T:
-        logits, target, ld_l, ld_t = logits.contiguous(), target.contiguous(), T, T
+    (logits, ld_l), (target, ld_t) = _lib.rows(logits), _lib.rows(target)
     out = torch.empty(K, dtype=torch.float32, device=logits.device)
-    _lib.call("rfd_bce_logits_rowsum", logits.device, K, T, logits.data_ptr(), int(ld_l), target.data_ptr(), int(ld_t),
+    _lib.call("rfd_bce_logits_rowsum", logits.device, K, T, logits.data_ptr(), ld_l, target.data_ptr(), ld_t,
               out.data_ptr())
     return out

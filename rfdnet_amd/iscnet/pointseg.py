@@ -147,14 +147,12 @@ def mask_loss_rows(logp, grouped_labels, proposal_labels, trans_feat, scale=0.00
     Kp, P, k = logp.shape
     assert k == 2 and trans_feat.shape == (Kp, 64, 64) and grouped_labels.shape == (Kp, P)
     logp = logp.float().contiguous()
-    lab = grouped_labels.to(dev).float()
-    if lab.stride(1) != 1 or (Kp > 1 and lab.stride(0) < P):
-        lab = lab.contiguous()
+    lab, ld = _lib.rows(grouped_labels.to(dev).float())
     want = proposal_labels.to(dev).reshape(Kp).long().contiguous()
     trans_feat = trans_feat.float().contiguous()
     partial = torch.empty(Kp, 2, dtype=torch.float64, device=dev)
     out = torch.empty(1, dtype=torch.float32, device=dev)
-    _lib.call("rfd_mask_loss_partial", dev, Kp, P, logp.data_ptr(), lab.data_ptr(), int(lab.stride(0)) if Kp > 1 else P,
+    _lib.call("rfd_mask_loss_partial", dev, Kp, P, logp.data_ptr(), lab.data_ptr(), ld,
               want.data_ptr(), trans_feat.data_ptr(), partial.data_ptr())
     _lib.call("rfd_mask_loss_finish", dev, Kp, P, float(scale), partial.data_ptr(), out.data_ptr())
     return out[0]

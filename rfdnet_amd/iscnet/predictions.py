@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from .. import _lib
+from .box_util import box_corners_upright_camera, class2angle, class2size  # noqa: F401  (re-exported)
 
 # configs/config_files/ISCNet_test.yaml:48-60 through config_utils.py:131-149
 DEFAULT_EVAL_CONFIG = {
@@ -38,32 +39,13 @@ def decode_boxes(end_points, dataset_config):
     heading_class = torch.argmax(end_points['heading_scores'], -1)
     heading_residuals = end_points['heading_residuals_normalized'] * (np.pi / nh)       # float32, as the reference
     heading_residual = torch.gather(heading_residuals, 2, heading_class.unsqueeze(-1)).squeeze(2)
-    angle = heading_class.double() * (2 * np.pi / float(nh)) + heading_residual.double()
-    angle = torch.where(angle > np.pi, angle - 2 * np.pi, angle)                        # class2angle
+    angle = class2angle(heading_class, heading_residual, nh)
     size_class = torch.argmax(end_points['size_scores'], -1)
     mean_size = torch.from_numpy(np.asarray(dataset_config.mean_size_arr)).to(center.device)
     size_residuals = end_points['size_residuals_normalized'] * mean_size.float().unsqueeze(0).unsqueeze(0)
     size_residual = torch.gather(size_residuals, 2,
                                  size_class.view(*size_class.shape, 1, 1).expand(-1, -1, 1, 3)).squeeze(2)
-    size = mean_size.double()[size_class] + size_residual.double()                       # class2size
-    return center, size, angle
-
-
-def box_corners_upright_camera(center, size, angle):
-    """get_3d_box(box_size, -heading, flip_axis_to_camera(center)) for every box
-    (box_util.py:183-198, libs.py:98-105) -> (B,K,8,3) float64."""
-    c = torch.cos(-angle)
-    s = torch.sin(-angle)
-    l, w, h = size[..., 0:1], size[..., 1:2], size[..., 2:3]
-    sx = torch.tensor([1, 1, -1, -1, 1, 1, -1, -1], dtype=torch.float64, device=center.device)
-    sy = torch.tensor([1, 1, 1, 1, -1, -1, -1, -1], dtype=torch.float64, device=center.device)
-    sz = torch.tensor([1, -1, -1, 1, 1, -1, -1, 1], dtype=torch.float64, device=center.device)
-    xc, yc, zc = l / 2 * sx, h / 2 * sy, w / 2 * sz
-    # roty(t) = [[c,0,s],[0,1,0],[-s,0,c]]
-    x = c.unsqueeze(-1) * xc + s.unsqueeze(-1) * zc
-    z = -s.unsqueeze(-1) * xc + c.unsqueeze(-1) * zc
-    cam = torch.stack([center[..., 0], -center[..., 2], center[..., 1]], -1)            # flip_axis_to_camera
-    return torch.stack([x + cam[..., 0:1], yc + cam[..., 1:2], z + cam[..., 2:3]], -1)
+    return center, class2size(size_class, size_residual, mean_size), angle
 
 
 @torch.no_grad()

@@ -17,7 +17,7 @@ def test_get_3d_box_matches_the_prediction_decoder_and_inverts():
     angle = (torch.rand(2, 5, generator=g, dtype=torch.float64) - 0.5) * 6.0
     want = predictions.box_corners_upright_camera(center, size, angle)        # pinned by F_NMS
     got = fit.get_3d_box(size, -angle, fit.flip_axis_to_camera(center))
-    assert torch.allclose(got, want, atol=1e-12)
+    assert torch.equal(got, want)                                             # one definition (iscnet/box_util.py)
     c, s, o = fit.box_params_from_corners(got.view(-1, 8, 3))
     assert torch.allclose(c, center.view(-1, 3), atol=1e-12) and torch.allclose(s, size.view(-1, 3), atol=1e-12)
     assert torch.allclose(torch.cos(o), torch.cos(angle.view(-1)), atol=1e-12)

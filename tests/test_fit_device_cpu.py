@@ -1,7 +1,8 @@
 """CPU: the pieces of fit_mesh_to_scan's device method that need no GPU -- the ragged float64 restatement tests/fit_f64.py
 (its analytic gradient against autograd on the reference's padded formulation, its fp32 Adam against torch.optim.Adam),
 the fixture tests/golden/F_FITD.npz (against the reference's run in F_FIT.npz, and against the restatement it was made
-with), and fit.prepare_fit's batched set-up against the per-object loop of method='autograd'."""
+with), and fit.prepare_fit's batched set-up and fit.padded_problem's tensors against the per-object loop below (the
+set-up written out one object at a time; it must stay independent of prepare_fit: fit.py's docstring)."""
 import os
 import re
 import shutil
@@ -167,7 +168,7 @@ def test_fixture_is_what_the_restatement_computes(golden_dir, fxd):
 
 # --------------------------------------------------------------------------------------------------------- 5. set-up
 def per_object_setup(meshes, proposal_ids, parsed_predictions, eval_dict, input_scan, dump_threshold):
-    """the set-up loop of fit.fit_mesh_to_scan(method='autograd'), with the scan rows it selects kept as indices
+    """the reference's set-up loop (network.py:196-269), one object at a time, with the scan rows it selects kept as indices
     -> index_list, scaled mesh points (V,3) f32, scan rows (index array), scan points (S,3) f32, start parameters"""
     corners_all = torch.as_tensor(np.asarray(parsed_predictions['pred_corners_3d_upright_camera'])).double()
     obj_prob = torch.as_tensor(np.asarray(parsed_predictions['obj_prob'])).double()
@@ -278,6 +279,45 @@ def test_prepare_fit_equals_the_per_object_setup(golden_dir):
     # four points per thread above the switch, or on request
     assert fit.prepare_fit(*args, points_per_thread=4).tile_start.tolist() == [0, 1024, 2048, 3072, 3536, 4560, 5584, 6608]
     assert fit.PPT_SWITCH == 65536
+
+
+def check_padded(args):
+    """the padded tensors of the reference's loop, built from the per-object set-up"""
+    want = per_object_setup(*args)
+    P = len(want)
+    obj = torch.zeros(P, fit.MAX_OBJ_POINTS, 3)
+    pc = torch.zeros(P, fit.MAX_PC_IN_BOX, 3)
+    mask = torch.zeros(P, fit.MAX_PC_IN_BOX)
+    for p, (_, scaled, rows, pts, par, sizes) in enumerate(want):
+        obj[p, :scaled.shape[0]] = scaled
+        pc[p, :pts.shape[0]] = pts
+        mask[p, :pts.shape[0]] = 1
+    par = torch.stack([w[4] for w in want])
+    got = fit.padded_problem(fit.prepare_fit(*args))
+    assert len(got) == 5 and all(g.dtype == torch.float32 for g in got)
+    for g, w in zip(got, (obj, pc, mask, par[:, :3], par[:, 3])):
+        assert g.shape == w.shape and torch.equal(g, w)
+    return P
+
+
+def test_padded_problem_equals_the_padded_per_object_setup(golden_dir):
+    _, args = f_fit_inputs(golden_dir)
+    assert check_padded(args) == 2
+    assert check_padded(random_scene()) == 8
+
+
+def test_autograd_method_with_nothing_to_fit_returns_the_boxes_untouched(monkeypatch):
+    meshes, ids, parsed, ev, scan, _ = random_scene()
+
+    def no_loop(*a, **k):
+        raise AssertionError("the optimisation loop was entered")
+    monkeypatch.setattr(fit, "chamfer_loss", no_loop)
+    monkeypatch.setattr(fit, "padded_problem", no_loop)
+    out = fit.fit_mesh_to_scan(meshes, ids, parsed, ev, scan, 2.0, method='autograd')
+    got = out['pred_corners_3d_upright_camera']
+    assert np.array_equal(got.numpy(), parsed['pred_corners_3d_upright_camera'])
+    assert not np.shares_memory(got.numpy(), parsed['pred_corners_3d_upright_camera'])
+    assert 'fit_indices' not in out and 'fit_loss' not in out
 
 
 def test_the_50000_point_cap_keeps_the_first_rows():

@@ -292,3 +292,34 @@ def test_estimate_normals_reruns_when_the_scale_came_down_while_it_folded(stub_s
     nrm = gen.estimate_normals(np.zeros((5, 3)), torch.zeros(4), torch.zeros(8), device="cpu")
     assert dec.runs == [3, 3] and dec.folds == 2 and left == []
     assert nrm.shape == (5, 3) and (nrm == 3).all()
+
+
+# ------------------------------------------------------------------------------------------------------ _lib.rows
+def test_rows_reads_row_strided_views_in_place_and_copies_the_rest():
+    base = torch.arange(15, dtype=torch.float32).view(3, 5)
+
+    def check(t, in_place, ld):
+        got, got_ld = _lib.rows(t)
+        assert torch.equal(got, t) and got_ld == ld and isinstance(got_ld, int)
+        assert (got.data_ptr() == t.data_ptr()) == in_place
+        K, T = t.shape
+        assert T <= 1 or got.stride(1) == 1
+        if K > 1:                                                    # row k starts ld elements after row k - 1
+            assert got.stride(0) == ld >= T
+        assert torch.equal(got.as_strided((K, T), (ld, 1)), t)     # what a kernel reads from (pointer, ld)
+        return got
+
+    check(base, True, 5)                                             # contiguous
+    wide = torch.arange(24, dtype=torch.float32).view(3, 8)
+    window = wide[:, 2:7]
+    assert window.shape == (3, 5) and not window.is_contiguous()
+    check(window, True, 8)                                           # a column window: read in place
+    assert check(base.t().contiguous().t(), False, 5).is_contiguous()                    # transposed: copied
+    assert check(base[:1].expand(3, 5), False, 5).is_contiguous()    # stride(0) == 0: rows overlap, copied
+    check(wide[1:2, 2:7], True, 5)                                   # one row of a wider tensor: ld = T
+    check(base.t()[1:2], False, 3)                                   # one row, not unit stride: copied, ld = T
+    col = wide[:, 3:4]
+    assert col.shape == (3, 1) and col.stride() == (8, 1)
+    check(col, True, 8)
+    odd = wide.as_strided((3, 1), (8, 5), 3)                         # T = 1: stride(1) is never stepped
+    check(odd, True, 8)

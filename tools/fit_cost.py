@@ -1,6 +1,7 @@
 """Cost of fit_mesh_to_scan on one GPU, both methods: 'autograd' (every object padded to 10 000 mesh rows and 50 000 scan
 rows, both Chamfer directions per step, the gradient through atomics, one host read per step) and 'device' (the ragged
-loop of csrc/fit_pose.hip) -- a comparison, not a test.
+loop of csrc/fit_pose.hip) -- a comparison, not a test.  Both legs start with the same batched set-up (fit.prepare_fit);
+the 'autograd' leg then pads it (fit.padded_problem).
 
     python tools/fit_cost.py [--out profiles/fit_stage.json] [--reps 3]
 
