@@ -7,6 +7,7 @@ write the reference's output files.
   python demo.py --synthetic 10 --out out/synth --upsampling_steps 1
   python demo.py --synthetic 10 --out out/synth --with_normals     (PLYs with per-vertex nx ny nz)
   python demo.py --synthetic 10 --out out/synth --refinement_step 30   (meshes refined against the occupancy field)
+  python demo.py --synthetic 10 --out out/synth --render --post_processing   (scene_objects.ply and pred.png as well)
 
 Weights: --weight <pretrained_weight.pth> (reference checkpoint, key names kept);
 without it seeded random weights are used (no pretrained weights ship with the
@@ -53,6 +54,14 @@ def build_parser():
     ap.add_argument("--refinement_step", type=int, default=None,
                     help="RMSprop steps of Generator3D.refine_mesh on every mesh (generation.refinement_step; the "
                          "reference's configs use 0 or 30)")
+    ap.add_argument("--render", action="store_true",
+                    help="place every mesh in its box (iscnet.scene.place_objects), render scan and meshes on the device "
+                         "and write scene_objects.ply and pred.png beside the other files (demo.py:329-377; needs "
+                         "--selection nms or --mode test: the boxes come from the parsed predictions)")
+    ap.add_argument("--render_size", type=int, nargs=2, default=(1024, 768), metavar=("W", "H"))
+    ap.add_argument("--post_processing", action="store_true",
+                    help="demo mode: refine the selected boxes with ISCNet.fit_mesh_to_scan(method='device') before the "
+                         "meshes are placed (the reference's post_processing=True, demo.py:273-275)")
     return ap
 
 
@@ -122,6 +131,11 @@ def main():
         end_points, ids, meshes, records = net.evaluate(data, completion=completion, losses=losses)
     else:
         end_points, ids, meshes = net.generate(data, selection=args.selection)
+    if args.post_processing and gt is None and len(meshes) and 'parsed_predictions' in end_points:
+        end_points['parsed_predictions'] = net.fit_mesh_to_scan(
+            {'meshes': meshes, 'proposal_ids': ids}, end_points['parsed_predictions'],
+            {'pred_mask': end_points['pred_mask']}, data['point_clouds'], cfg.config['generation']['dump_threshold'],
+            method='device')
     torch.cuda.synchronize()
     print('Time elapsed: %s.' % (time.time() - t0))                       # demo.py:411
     if records is not None:
@@ -144,6 +158,15 @@ def main():
         keep[ids[0, :, 0].cpu().numpy()] = True
     io.save_visualization(args.out, data['point_clouds'].cpu().numpy(), ids[0].cpu().numpy(), meshes, box, keep)
     print('%d meshes written to %s' % (len(meshes), args.out))
+    if args.render:
+        if 'parsed_predictions' not in end_points:
+            raise SystemExit("--render needs the boxes of --selection nms (or --mode test)")
+        from rfdnet_amd import render
+        from rfdnet_amd.iscnet.scene import place_objects
+        scene = place_objects(meshes, ids, end_points['parsed_predictions'], with_normals=args.with_normals)
+        camera = render.Camera.fit(data['point_clouds'][0], width=args.render_size[0], height=args.render_size[1])
+        io.save_scene(args.out, scene, render.render_scene(scene, data['point_clouds'], camera))
+        print('scene_objects.ply and pred.png written to %s' % args.out)
 
 
 if __name__ == "__main__":

@@ -17,7 +17,7 @@ _fl = C.c_float
 _sz = C.c_size_t
 
 # name -> (restype, argtypes[, OPTIONAL]): exactly the prototypes of include/rfd_pointnet2.h / rfd_occ.h /
-# rfd_chamfer.h / rfd_eval.h / rfd_latent.h / rfd_loss.h / rfd_fit.h.  OPTIONAL marks the test hooks, which a deployment build (RFD_NO_TEST_HOOKS=1, build.py)
+# rfd_chamfer.h / rfd_eval.h / rfd_latent.h / rfd_loss.h / rfd_fit.h / rfd_render.h.  OPTIONAL marks the test hooks, which a deployment build (RFD_NO_TEST_HOOKS=1, build.py)
 # leaves out.
 OPTIONAL = "optional"
 ABI = {
@@ -98,6 +98,9 @@ ABI = {
     "rfd_mask_loss_finish": (_i, [_i, _i, _fl, _f, _f, _f]),
     "rfd_fit_pose_run": (_i, [_i, _i, _i, _i, _i, _i, C.c_double, C.c_double, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f,
                               _f, _f]),
+    "rfd_raster_project": (_i, [_i, _i, _i, _f, _f, C.POINTER(C.c_double), C.c_double, _f, _f, _f, _f]),
+    "rfd_raster_triangles": (_i, [_i, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f]),
+    "rfd_raster_shade": (_i, [_i, _i, _i, _i, _i, _f, _f, _f, _f, _f, C.POINTER(C.c_double), _f, _f, _f, _f, _f]),
     "rfd_last_error_string": (C.c_char_p, []),
     "rfd_build_arch": (C.c_char_p, []),
     "rfd_device_status": (_i, []),

@@ -10,9 +10,13 @@
   write_points_ply    `%06d_pc.ply` (pc_util.write_ply)
   save_visualization  demo.py:278-327: meshes + `%06d_pred_confident_nms_bbox.npz`
                       with obbs (K,7) and proposal_map (K,1)
+  write_png           8-bit RGB, no interlace, by zlib and struct alone
+  save_scene          what the reference's `visualize` shows (demo.py:329-377), as files: the
+                      placed objects in one mesh `scene_objects.ply` and the picture `pred.png`
 """
 import os
 import struct
+import zlib
 
 import numpy as np
 
@@ -153,3 +157,29 @@ def save_visualization(output_dir, point_clouds, proposal_ids, meshes, box_param
             bp = bp[np.asarray(keep_mask, dtype=bool)]
         np.savez(os.path.join(output_dir, '%06d_pred_confident_nms_bbox.npz' % batch_id),
                  obbs=bp, proposal_map=ids.astype(np.int64))
+
+
+def write_png(path, image):
+    """image (H,W,3) uint8 -> an 8-bit RGB PNG without interlace (filter 0 on every row)"""
+    img = np.ascontiguousarray(np.asarray(image))
+    if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3 or img.shape[0] < 1 or img.shape[1] < 1:
+        raise ValueError("write_png: an (H,W,3) uint8 image, got %s %s" % (img.dtype, img.shape))
+    h, w = img.shape[:2]
+    rows = np.concatenate([np.zeros((h, 1), np.uint8), img.reshape(h, w * 3)], 1)
+
+    def chunk(kind, data):
+        return struct.pack(">I", len(data)) + kind + data + struct.pack(">I", zlib.crc32(kind + data) & 0xffffffff)
+    with open(path, "wb") as fh:
+        fh.write(b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 2, 0, 0, 0)) +
+                 chunk(b"IDAT", zlib.compress(rows.tobytes(), 6)) + chunk(b"IEND", b""))
+
+
+def save_scene(output_dir, scene_mesh, render=None):
+    """scene_objects.ply: the placed objects of iscnet.scene.place_objects as one mesh (with nx ny nz if it has normals);
+    pred.png: render.image of rfdnet_amd.render.render_scene, if given"""
+    os.makedirs(output_dir, exist_ok=True)
+    host = lambda t: None if t is None else t.cpu().numpy() if hasattr(t, "cpu") else np.asarray(t)
+    write_mesh_ply(os.path.join(output_dir, 'scene_objects.ply'), host(scene_mesh.vertices), host(scene_mesh.faces),
+                   host(scene_mesh.normals))
+    if render is not None:
+        write_png(os.path.join(output_dir, 'pred.png'), host(render.image))

@@ -1,0 +1,107 @@
+"""Cost of the scene render on one GPU -- a record, not a test.
+
+    python tools/render_cost.py [--out profiles/render_cost.json] [--reps 20] [--warmup 3]
+
+Two scenes at 1024x768 with 80 000 scan points (rfdnet_amd.synthetic, seed 100): the demo-sized one with 13 objects and
+the headline one with 256.  The objects are marching-cubes meshes of dented spheres at 48^3 (about 18 600 faces each,
+the order of the generator's meshes), in the synthetic scene's boxes (used again with other centres and headings as often
+as needed).  Per scene: device milliseconds of render_scene (HIP events around the call, the median, minimum and maximum of
+`reps` calls after `warmup`), of place_objects the same way, the primitive counts, the covered pixels, and beside them
+the scene's own reconstruction time from the benchmark records profiles/r06_bench_demo.json / r06_bench_headline.json."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import types
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+GRID = 48
+
+
+def event_ms(fn):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b)
+
+
+def timed(fn, reps, warmup):
+    for _ in range(warmup):
+        fn()
+    ms = [event_ms(fn) for _ in range(reps)]
+    return {"ms": statistics.median(ms), "ms_min": min(ms), "ms_max": max(ms)}
+
+
+def scene_inputs(n_obj, points=80000):
+    from rfdnet_amd import synthetic
+    from rfdnet_amd.iscnet import box_util
+    from rfdnet_amd.iscnet.mcubes import marching_cubes_batch
+    pc, boxes, _ = synthetic.synthetic_scene(seed=100, n_raw=int(points * 1.5), n_points=points, return_boxes=True)
+    rng = np.random.default_rng(5)
+    again = np.arange(n_obj) >= len(boxes)                                       # a box used again: somewhere else
+    boxes = boxes[np.arange(n_obj) % len(boxes)].astype(np.float64)
+    centre = boxes[:, :3] + again[:, None] * rng.uniform(-1.5, 1.5, (n_obj, 3)) * (1., 1., 0.)
+    heading = boxes[:, 6] + rng.normal(0, 0.3, n_obj)
+    corners = box_util.box_corners_upright_camera(torch.from_numpy(centre), torch.from_numpy(boxes[:, 3:6]),
+                                                  torch.from_numpy(heading))[None].cuda()
+    g = np.stack(np.meshgrid(*[np.arange(GRID, dtype=np.float32)] * 3, indexing='ij'), -1) - (GRID - 1) / 2.
+    r = np.linalg.norm(g, axis=-1)
+    grids = torch.empty(n_obj, GRID, GRID, GRID, device="cuda")
+    for k in range(n_obj):                                                       # a sphere with a few dents of its own
+        w = rng.normal(0, 1, 3)
+        grids[k] = torch.from_numpy((0.45 * GRID - r + 1.5 * np.sin(g @ w / 4.)).astype(np.float32))
+    meshes = [types.SimpleNamespace(vertices=v, faces=f) for v, f in marching_cubes_batch(grids, 0.)]
+    parsed = {'pred_corners_3d_upright_camera': corners,
+              'pred_sem_cls': torch.from_numpy(rng.integers(0, 18, (1, n_obj))).cuda()}
+    return meshes, torch.arange(n_obj).view(1, n_obj, 1), parsed, torch.from_numpy(pc[None]).cuda()
+
+
+def measure(label, n_obj, record, reps, warmup):
+    from rfdnet_amd import render
+    from rfdnet_amd.iscnet.scene import place_objects
+    meshes, ids, parsed, scan = scene_inputs(n_obj)
+    camera = render.Camera.fit(scan, width=1024, height=768)
+    scene = place_objects(meshes, ids, parsed)
+    out = render.render_scene(scene, scan, camera)
+    F = int(scene.faces.shape[0])
+    row = {"scene": label, "objects": n_obj, "vertices": int(scene.vertices.shape[0]), "faces": F,
+           "scan_points": int(scan.shape[1]), "image": [1024, 768], "point_px": 3, "launches": 3, "clears": 1,
+           "pixels_on_faces": int(((out.ids >= 0) & (out.ids < F)).sum()), "pixels_on_points": int((out.ids >= F).sum()),
+           "render_scene": timed(lambda: render.render_scene(scene, scan, camera), reps, warmup),
+           "place_objects": timed(lambda: place_objects(meshes, ids, parsed), reps, warmup)}
+    with open(os.path.join(ROOT, "profiles", record)) as f:
+        bench = json.load(f)
+    row["reconstruction"] = {"record": "profiles/" + record, "ms_per_step": bench["ms_per_step"], "metric": bench["metric"]}
+    return row
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("render_cost measures on a GPU: none is visible")
+    rows = [measure("demo-sized", 13, "r06_bench_demo.json", args.reps, args.warmup),
+            measure("headline", 256, "r06_bench_headline.json", args.reps, args.warmup)]
+    result = {"tool": "render_cost", "device": torch.cuda.get_device_name(0), "reps": args.reps, "warmup": args.warmup,
+              "rows": rows}
+    text = json.dumps(result)
+    print(text)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(text + "\n")
+
+
+if __name__ == "__main__":
+    main()
