@@ -22,7 +22,7 @@ NaN recall, which makes 'AR' NaN.
 import numpy as np
 import torch
 
-from .. import _lib
+from .. import _lib, ragged
 from . import box_util, predictions
 
 MAX_THRESHOLDS = 4
@@ -341,9 +341,10 @@ def records_from_lists(batch_pred_map_cls, batch_gt_map_cls, ap_iou_thresh):
                       up(gtc[i:i + LIST_GROUPS]), torch.zeros(min(LIST_GROUPS, b - i), Gp, dtype=torch.int32, device=dev),
                       up(gt_valid[i:i + LIST_GROUPS]), thr) for i in range(0, b, LIST_GROUPS)]
     rec = merge_records(parts, thr)
-    # compact() walks the (group, detection) pairs in row-major order: the class of a record is its group's
+    # compact() walks the (group, detection) pairs in row-major order: the class of a record is its group's (the owner
+    # map of DESIGN.md "Ragged batches")
     counts = valid[:, 0].sum(1, dtype=np.int64)
-    cls = np.repeat(np.array([k[1] for k in keys], np.int32), counts)
+    cls = np.array([k[1] for k in keys], np.int32)[ragged.owners(counts)]
     return {'cls': cls, 'score': rec['score'], 'tp': rec['tp'], 'npos': npos, 'thr': thr}
 
 

@@ -42,7 +42,7 @@ import numpy as np
 import torch
 
 from ..chamfer_distance import ChamferDistanceFunction
-from .. import _lib
+from .. import _lib, ragged
 from .box_util import box_params_from_corners, flip_axis_to_camera, flip_axis_to_depth, get_3d_box  # noqa: F401
 
 MAX_OBJ_POINTS = 10000          # network.py:194
@@ -83,6 +83,7 @@ def chamfer_loss(obj_points, pc_in_box, pc_in_box_masks, centroid_params, orient
 
 
 METHODS = ('autograd', 'device')
+RUN_WIDTH = 256                 # csrc/fit_pose.hip's WG: a run (tile) is RUN_WIDTH * points_per_thread scan rows of one object
 PPT_SWITCH = 65536              # scan points of all objects together: up to here fit_nn_kernel takes one point per thread
 
 
@@ -123,8 +124,8 @@ def normalise_mesh_points_ragged(vertices, seg, n_obj):
 
 
 class FitProblem(object):
-    """The ragged problem of rfd_fit_pose_run (include/rfd_fit.h) and what finish_fit needs beside it:
-    obj (n_obj,3) f32, obj_off (P+1) i32, scan (n_scan,3) f32, scan_off (P+1) i32, tile_obj / tile_start (n_tiles) i32,
+    """The ragged problem of rfd_fit_pose_run (include/rfd_fit.h; DESIGN.md "Ragged batches") and what finish_fit needs
+    beside it: obj (n_obj,3) f32, obj_off (P+1) i32, scan (n_scan,3) f32, scan_off (P+1) i32, tile_obj / tile_start (n_tiles) i32,
     scan_index (n_scan) i64: the row of its scene's input scan that every row of `scan` is,
     params0 (P,4) f32, sizes (P,3) f64, corners (B,K,8,3) f64: the boxes as they came in, index_list: the (scene,
     proposal) of every object, n_vertices / n_scan_points: per object, on the host, points_per_thread, loss_scale;
@@ -132,18 +133,6 @@ class FitProblem(object):
 
     def __init__(self, **kw):
         self.__dict__.update(kw)
-
-
-def fit_tiles(n_scan_points, points_per_thread):
-    """per-object scan counts -> (tile_obj, tile_start) int32 arrays: an object's rows in runs of 256 * points_per_thread"""
-    step = 256 * points_per_thread
-    tile_obj, tile_start, at = [], [], 0
-    for p, n in enumerate(n_scan_points):
-        for s in range(at, at + n, step):
-            tile_obj.append(p)
-            tile_start.append(s)
-        at += n
-    return np.asarray(tile_obj, np.int32), np.asarray(tile_start, np.int32)
 
 
 def prepare_fit(meshes, proposal_ids, parsed_predictions, eval_dict, input_scan, dump_threshold, points_per_thread=None):
@@ -179,7 +168,7 @@ def prepare_fit(meshes, proposal_ids, parsed_predictions, eval_dict, input_scan,
         kt = torch.as_tensor(keep, device=dev)
         row, col = torch.nonzero(inside[kt], as_tuple=True)                  # row-major: every object's points in scan order
         if max(n_in[k] for k in keep) > MAX_PC_IN_BOX:
-            first = np.concatenate([[0], np.cumsum([n_in[k] for k in keep])[:-1]])
+            first = ragged.offsets([n_in[k] for k in keep])[:-1]
             rank = torch.arange(row.shape[0], device=dev) - torch.as_tensor(first, device=dev)[row]
             col = col[rank < MAX_PC_IN_BOX]
         scan_parts.append(scene_scan[col])
@@ -202,16 +191,15 @@ def prepare_fit(meshes, proposal_ids, parsed_predictions, eval_dict, input_scan,
         vert_list[k] = verts.to(dev, torch.float64)
         n_vertices.append(int(verts.shape[0]))
     centroid, sizes, orientation = (torch.cat([b[c] for b in box_parts]) for c in range(3))
-    seg_host = np.repeat(np.arange(P), n_vertices)
+    seg_host = ragged.owners(n_vertices)
     seg = torch.from_numpy(seg_host).to(dev)
     scaled = normalise_mesh_points_ragged(torch.cat(vert_list), seg, P) * sizes[seg]
     # one zero row after every mesh that the reference would pad: it stands for all its padded rows (module docstring)
     extra = np.asarray([v < MAX_OBJ_POINTS for v in n_vertices], np.int64)
-    obj_off = np.concatenate([[0], np.cumsum(np.asarray(n_vertices) + extra)])
-    scan_off = np.concatenate([[0], np.cumsum(n_scan_points)])
-    assert obj_off[-1] < 2 ** 31 and scan_off[-1] < 2 ** 31
+    obj_off = ragged.offsets(np.asarray(n_vertices) + extra)
+    scan_off = ragged.offsets(n_scan_points)
     obj = torch.zeros(int(obj_off[-1]), 3, dtype=torch.float32, device=dev)
-    dest = np.arange(len(seg_host)) + (np.cumsum(extra) - extra)[seg_host]
+    dest = np.arange(len(seg_host)) + ragged.offsets(extra)[seg_host]
     obj[torch.from_numpy(dest).to(dev)] = scaled.float()
     return ragged_problem(obj, obj_off, torch.cat(scan_parts).float().contiguous(), scan_off,
                           torch.cat([centroid.float(), orientation.float()[:, None]], 1).contiguous(),
@@ -221,15 +209,16 @@ def prepare_fit(meshes, proposal_ids, parsed_predictions, eval_dict, input_scan,
 
 def ragged_problem(obj, obj_off, scan, scan_off, params0, loss_scale, points_per_thread=None, **more):
     """obj (n_obj,3), scan (n_scan,3), params0 (P,4): f32 tensors on the problem's device; obj_off, scan_off (P+1): host
-    integer arrays -> FitProblem with the tiling of points_per_thread (default: 1 up to PPT_SWITCH scan points, else 4)"""
+    integer arrays -> FitProblem with the runs (tile_obj / tile_start, DESIGN.md "Ragged batches") of points_per_thread
+    (default: 1 up to PPT_SWITCH scan points, else 4)"""
     dev = obj.device
     n_scan_points = [int(n) for n in np.diff(scan_off)]
     if points_per_thread is None:
         points_per_thread = 1 if scan_off[-1] <= PPT_SWITCH else 4
-    tile_obj, tile_start = fit_tiles(n_scan_points, points_per_thread)
-    i32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.int32)).to(dev)
-    return FitProblem(P=len(n_scan_points), device=dev, obj=obj, obj_off=i32(obj_off), scan=scan, scan_off=i32(scan_off),
-                      n_scan_points=n_scan_points, tile_obj=i32(tile_obj), tile_start=i32(tile_start),
+    tile_obj, tile_start = ragged.runs(n_scan_points, RUN_WIDTH * points_per_thread)
+    return FitProblem(P=len(n_scan_points), device=dev, obj=obj, obj_off=ragged.to_int32(obj_off, dev), scan=scan,
+                      scan_off=ragged.to_int32(scan_off, dev), n_scan_points=n_scan_points,
+                      tile_obj=ragged.to_int32(tile_obj, dev), tile_start=ragged.to_int32(tile_start, dev),
                       points_per_thread=points_per_thread, params0=params0, loss_scale=loss_scale, result=None, **more)
 
 

@@ -17,8 +17,8 @@ import os
 import numpy as np
 import torch
 
-from .. import _lib
-from .occ_decoder import MODE_F16X3, TILE, logit_threshold, run_with_range_fallback
+from .. import _lib, ragged
+from .occ_decoder import GROUP, MODE_F16X3, TILE, logit_threshold, run_with_range_fallback
 
 
 class Mesh(object):
@@ -144,7 +144,8 @@ class Generator3D(object):
     @torch.no_grad()
     def _grids(self, z, c, fold_out=None):
         """fold_out (a list): receives the (table, fc_p_w) this call folded -- passed along by argument, not kept in an
-        attribute (worker_view() copies the generator per host thread)"""
+        attribute (worker_view() copies the generator per host thread).  The query lists are padded 128-point tiles
+        (DESIGN.md "Ragged batches"): uniform here, per proposal and per round in _grids_mise."""
         dec = self.model.decoder
         dev = c.device
         K = c.size(0)
@@ -155,12 +156,11 @@ class Generator3D(object):
         if self.upsampling_steps == 0:                                      # :91-97 dense shortcut
             nx = self.resolution0
             total = nx ** 3
-            tiles_per = (total + TILE - 1) // TILE
+            tiles_per = int(ragged.blocks(total, TILE))
             pts = torch.empty(tiles_per * TILE, 3, dtype=torch.float32, device=dev)
             _lib.call("rfd_make_grid_points", dev, nx, -0.5, 0.5, float(box_size), pts.data_ptr(),
                       tiles_per * TILE)
-            tile_prop = torch.arange(K, dtype=torch.int32, device=dev).repeat_interleave(tiles_per)
-            tile_src = torch.arange(tiles_per, dtype=torch.int32, device=dev).repeat(K)
+            tile_prop, tile_src = ragged.uniform_maps(K, tiles_per, dev)
             logits = dec.decode_tiles(pts, tile_prop, table, fc_p_w, tile_src=tile_src)
             self.stats = {'n_queries': K * total, 'rounds': 1, 'per_round': [K * total]}
             return logits.view(K, tiles_per * TILE)[:, :total].reshape(K, nx, nx, nx)
@@ -196,12 +196,11 @@ class Generator3D(object):
                 total = int(cnt.sum())
                 if total == 0:                                               # generator.py:104
                     break
-                tiles = (cnt + TILE - 1) // TILE
-                offs = np.concatenate([[0], np.cumsum(tiles)[:-1]]) * TILE
-                n_tiles = int(tiles.sum())
-                tile_prop = torch.from_numpy(np.repeat(np.arange(K, dtype=np.int32), tiles)).to(dev)
+                tiles = ragged.padded_tiles(cnt, TILE)                       # DESIGN.md "Ragged batches"
+                n_tiles = int(tiles.prefix[-1])
+                tile_prop = ragged.to_int32(tiles.owner, dev)
                 tile_src = None
-                offsets = torch.from_numpy(offs.astype(np.int32)).to(dev)
+                offsets = ragged.to_int32(tiles.slot[:-1], dev)
                 cursors = torch.zeros(K, dtype=torch.int32, device=dev)
                 pts = torch.zeros(n_tiles * TILE, 3, dtype=torch.float32, device=dev)
                 lin = torch.full((n_tiles * TILE,), -1, dtype=torch.int32, device=dev)
@@ -238,7 +237,8 @@ class Generator3D(object):
         """The query list of MISE round 0 for K proposals: the list of ONE freshly initialised
         proposal (built once per configuration by the ordinary count / collect kernels, so it is
         bit-identical to what they would produce for every proposal) plus tile maps that make
-        all K proposals read it.  Returns (pts, lin, tile_prop, tile_src, K * points)."""
+        all K proposals read it (the uniform maps of DESIGN.md "Ragged batches").  Returns (pts, lin, tile_prop,
+        tile_src, K * points)."""
         def build():
             R1 = (res0 << depth) + 1
             ps = torch.empty(1, R1 ** 3, dtype=torch.uint8, device=dev)
@@ -247,16 +247,14 @@ class Generator3D(object):
             _lib.call("rfd_mise_init", dev, 1, res0, depth, ps.data_ptr(), vs.data_ptr())
             _lib.call("rfd_mise_count", dev, 1, res0, depth, ps.data_ptr(), cnt.data_ptr())
             n = int(cnt.item())
-            tiles_per = (n + TILE - 1) // TILE
+            tiles_per = int(ragged.blocks(n, TILE))
             pts = torch.zeros(tiles_per * TILE, 3, dtype=torch.float32, device=dev)
             lin = torch.full((tiles_per * TILE,), -1, dtype=torch.int32, device=dev)
             offsets = torch.zeros(1, dtype=torch.int32, device=dev)
             cursors = torch.zeros(1, dtype=torch.int32, device=dev)
             _lib.call("rfd_mise_collect", dev, 1, res0, depth, ps.data_ptr(), offsets.data_ptr(),
                       cursors.data_ptr(), float(box_size), pts.data_ptr(), lin.data_ptr())
-            tile_prop = torch.arange(K, dtype=torch.int32, device=dev).repeat_interleave(tiles_per)
-            tile_src = torch.arange(tiles_per, dtype=torch.int32, device=dev).repeat(K)
-            return pts, lin, tile_prop, tile_src, K * n
+            return (pts, lin) + ragged.uniform_maps(K, tiles_per, dev) + (K * n,)
         return self._round0_cache.get((res0, depth, float(box_size), K, str(dev)), build, dev)   # per K: NMS changes it
 
     # ---- mesh extraction ------------------------------------------------------------
@@ -303,8 +301,8 @@ class Generator3D(object):
     def refine_meshes(self, v, f, vend, tend, fold, steps, eps=None, return_grad=False):
         """Generator3D.refine_mesh for ALL meshes of the flat marching-cubes buffers in one device loop (csrc/mesh_refine.hip):
         v (V,3) f64 / f32 vertices, f (F,3) i32 faces with indices local to their mesh, vend / tend the K + 1 vertex / face
-        offsets, fold = (table, fc_p_w) of the K codes.  -> refined vertices (V,3) f32 (a new tensor: v is the kept v0)
-        [, the first step's vertex gradient (V,3) f32].  eps: the weights, (steps, F, 3), instead of a draw (set_refinement's
+        offsets (the tile and group maps made from them here: DESIGN.md "Ragged batches"), fold = (table, fc_p_w) of the K
+        codes.  -> refined vertices (V,3) f32 (a new tensor: v is the kept v0) [, the first step's vertex gradient (V,3) f32].  eps: the weights, (steps, F, 3), instead of a draw (set_refinement's
         eps_source).  Every mesh has its own loss (its own means) and its own RMSprop state, as in the reference's per-object
         loop; empty meshes take no part.  Asynchronous, no host round trip inside the loop: the f16-range flag (STATUS_DECODER_RANGE)
         is left in the stream's status word for the caller's run_with_range_fallback, which starts again from v0."""
@@ -323,12 +321,10 @@ class Generator3D(object):
             table, fc_p_w = fold
             assert table.shape[0] >= K
             counts = [tend[k + 1] - tend[k] for k in range(K)]
-            tiles = [(n + TILE - 1) // TILE for n in counts]
-            tprefix = np.concatenate([[0], np.cumsum(tiles)])
-            gprefix = np.concatenate([[0], np.cumsum([(n + 15) // 16 for n in counts])])
-            bounds = torch.from_numpy(np.stack([tend, vend, tprefix, gprefix]).astype(np.int32)).to(dev)
-            fend_d, vend_d, tprefix_d, gprefix_d = bounds[0], bounds[1], bounds[2], bounds[3]
-            tile_prop = torch.from_numpy(np.repeat(np.arange(K, dtype=np.int32), tiles)).to(dev)
+            tiles = ragged.padded_tiles(counts, TILE)
+            gprefix = ragged.offsets(ragged.blocks(counts, GROUP))
+            fend_d, vend_d, tprefix_d, gprefix_d = ragged.to_int32(np.stack([tend, vend, tiles.prefix, gprefix]), dev)
+            tile_prop = ragged.to_int32(tiles.owner, dev)
             faces = f[:F].to(torch.int32).contiguous()
             first = torch.repeat_interleave(vend_d[:-1].long(), torch.as_tensor(counts, device=dev), output_size=F)
             rowptr, col = vertex_corner_csr(faces.long() + first[:, None], V)
@@ -341,7 +337,7 @@ class Generator3D(object):
             else:
                 seed = self.refine_seed if self.refine_seed is not None else int(np.random.randint(0, 2 ** 31 - 1))
             qd = torch.empty(F, 3, dtype=torch.float64, device=dev)
-            qt = torch.zeros(int(tprefix[-1]) * TILE, 3, dtype=torch.float32, device=dev)     # padding slots stay zero
+            qt = torch.zeros(int(tiles.slot[-1]), 3, dtype=torch.float32, device=dev)     # padding slots stay zero
             cg = torch.empty(F, 3, 3, dtype=torch.float64, device=dev)     # f64: csrc/mesh_refine.hip's header says why
             sq = torch.zeros(V, 3, dtype=torch.float32, device=dev)
             g = torch.empty(F, 3, dtype=torch.float32, device=dev)

@@ -18,11 +18,12 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from .. import _lib, occ_fold
+from .. import _lib, occ_fold, ragged
 
 MODE_F16X3 = 3   # parity mode (fp32-class logits)
 MODE_F16X1 = 1   # throughput mode
-TILE = 128
+TILE = 128       # RFD_OCC_TILE: query points of a decoder tile (include/rfd_occ.h)
+GROUP = 16       # vertices of a group of rfd_occ_normals_w8's `gprefix` (include/rfd_occ.h)
 
 
 def logit_threshold(threshold):
@@ -157,7 +158,8 @@ class DecoderCBatchNorm(nn.Module):
     def normals(self, verts, vend, table, fc_p_w, return_grad=False):
         """Vertex normals -g / |g|, g = d logit / d p, of K meshes in one launch (csrc/occ_normals.hip;
         Generator3D.estimate_normals, generator.py:200-224).
-        verts (V,3) f64 device tensor (all meshes back to back), vend: K + 1 vertex offsets (list or sequence), table /
+        verts (V,3) f64 device tensor (all meshes back to back), vend: K + 1 vertex offsets (list or sequence; the group
+        prefix they imply: DESIGN.md "Ragged batches"), table /
         fc_p_w: the fold of the meshes' codes (fold()).  -> normals (V,3) f32 [, grad (V,3) f32].  A vertex whose gradient
         is exactly zero gets NaN (0/0, as in the reference).  Asynchronous: the f16-range flag (STATUS_DECODER_RANGE) is left in
         the stream's status word for the caller to read, like decode_tiles()."""
@@ -170,17 +172,14 @@ class DecoderCBatchNorm(nn.Module):
         vend = [int(x) for x in vend]
         K = len(vend) - 1
         assert K >= 1 and vend[0] == 0 and vend[-1] <= verts.shape[0] and table.shape[0] >= K
-        counts = [vend[k + 1] - vend[k] for k in range(K)]
-        gprefix = [0]
-        for n in counts:
-            gprefix.append(gprefix[-1] + (n + 15) // 16)
+        gprefix = ragged.offsets(ragged.blocks(np.diff(vend), GROUP))
         V = vend[-1]
         dev = verts.device
         normals = torch.empty(V, 3, dtype=torch.float32, device=dev)
         grad = torch.empty(V, 3, dtype=torch.float32, device=dev) if return_grad else None
         if gprefix[-1]:
-            bounds = torch.tensor([vend, gprefix], dtype=torch.int32).to(dev, non_blocking=True)
-            self.input_grad_launcher(table, fc_p_w, K, gprefix[-1], bounds[0], bounds[1])(verts, normals, grad)
+            vend_d, gprefix_d = ragged.to_int32(np.stack([vend, gprefix]), dev, non_blocking=True)
+            self.input_grad_launcher(table, fc_p_w, K, int(gprefix[-1]), vend_d, gprefix_d)(verts, normals, grad)
         return (normals, grad) if return_grad else normals
 
     def input_grad_launcher(self, table, fc_p_w, K, n_groups, vend, gprefix):
@@ -281,7 +280,8 @@ class DecoderCBatchNorm(nn.Module):
         return logits
 
     def forward(self, p, z, c, **kwargs):
-        """p (B,T,3), z (B,Z), c (B,C) -> logits (B,T).  occ_decoder.py:110-123.
+        """p (B,T,3), z (B,Z), c (B,C) -> logits (B,T).  occ_decoder.py:110-123.  B uniform segments of padded tiles
+        (DESIGN.md "Ragged batches").
 
         Gradients: when p requires grad (and grad mode is on) the logits carry a grad_fn whose backward gives
         dL/dp = dL/dlogit * d logit / d p through the normals kernel (csrc/occ_normals.hip) -- what the reference's
@@ -297,14 +297,14 @@ class DecoderCBatchNorm(nn.Module):
         B, T, _ = p.shape
         if c.dim() == 3:
             c = c.squeeze(2)
-        tpad = (T + TILE - 1) // TILE * TILE
+        tiles_per = int(ragged.blocks(T, TILE))
+        tpad = tiles_per * TILE
         if tpad != T:
             pp = torch.zeros(B, tpad, 3, dtype=torch.float32, device=p.device)
             pp[:, :T] = p
         else:
             pp = p.contiguous().float()
-        tiles_per = tpad // TILE
-        tile_prop = torch.arange(B, dtype=torch.int32, device=p.device).repeat_interleave(tiles_per)
+        tile_prop, _ = ragged.uniform_maps(B, tiles_per, p.device, src=False)
 
         def run():
             table, fc_p_w = self.fold(z.float(), c.float())

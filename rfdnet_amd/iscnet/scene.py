@@ -24,14 +24,14 @@ the permutation and the rotation are orthogonal and apply as they are; the resul
 import numpy as np
 import torch
 
-from .. import _lib
+from .. import _lib, ragged
 from .box_util import box_params_from_corners
 from .fit import TRANSFORM_SHAPENET, normalise_mesh_points_ragged
 
 
 class SceneMesh(object):
-    """The placed objects as one ragged mesh: vertices (V,3) f32 in scan coordinates, faces (F,3) i32 into `vertices`,
-    face_obj (F) i32: the object of every face, obj_off / face_off (K'+1) i32: object k owns the vertex rows
+    """The placed objects as one ragged mesh (DESIGN.md "Ragged batches"): vertices (V,3) f32 in scan coordinates,
+    faces (F,3) i32 into `vertices`, face_obj (F) i32: the object of every face, obj_off / face_off (K'+1) i32: object k owns the vertex rows
     obj_off[k] .. obj_off[k+1] and the face rows face_off[k] .. face_off[k+1], obj_class (K') i32: its semantic class,
     normals (V,3) f32 or None."""
 
@@ -56,16 +56,13 @@ def place_objects(meshes, proposal_ids, parsed_predictions, with_normals=False):
     dev = verts[0].device if K else corners_all.device if torch.is_tensor(corners_all) else torch.device('cpu')
     n_v = np.asarray([v.shape[0] for v in verts], np.int64)
     n_f = np.asarray([f.shape[0] if v.shape[0] else 0 for v, f in zip(verts, faces)], np.int64)
-    obj_off = np.concatenate([[0], np.cumsum(n_v)])
-    face_off = np.concatenate([[0], np.cumsum(n_f)])
-    if obj_off[-1] >= 2 ** 31 or face_off[-1] >= 2 ** 31:
-        raise ValueError("place_objects: more than 2^31 vertices or faces")
-    i32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.int32)).to(dev)
+    obj_off, face_off = ragged.offsets(n_v), ragged.offsets(n_f)
     sem = parsed_predictions.get('pred_sem_cls')
     rows = torch.from_numpy(ids).to(dev)
     obj_class = torch.zeros(K, dtype=torch.int32, device=dev) if sem is None else \
         _lib.as_tensor(sem, dev, torch.int64)[0][rows].to(torch.int32)
-    out = SceneMesh(obj_off=i32(obj_off), face_off=i32(face_off), obj_class=obj_class, normals=None)
+    out = SceneMesh(obj_off=ragged.to_int32(obj_off, dev), face_off=ragged.to_int32(face_off, dev), obj_class=obj_class,
+                    normals=None)
     if obj_off[-1] == 0:
         out.vertices = torch.zeros(0, 3, dtype=torch.float32, device=dev)
         out.faces = torch.zeros(0, 3, dtype=torch.int32, device=dev)
@@ -76,7 +73,7 @@ def place_objects(meshes, proposal_ids, parsed_predictions, with_normals=False):
 
     corners = _lib.as_tensor(corners_all, dev, torch.float64)[0][rows]
     centre, sizes, theta = box_params_from_corners(corners)
-    seg = torch.from_numpy(np.repeat(np.arange(K), n_v)).to(dev)
+    seg = torch.from_numpy(ragged.owners(n_v)).to(dev)
     v = torch.cat([x.to(dev, torch.float64) for x in verts])
     v = normalise_mesh_points_ragged(v, seg, K) * sizes[seg]                    # steps 1-4
     c, s = torch.cos(theta)[seg], torch.sin(theta)[seg]
@@ -86,10 +83,11 @@ def place_objects(meshes, proposal_ids, parsed_predictions, with_normals=False):
         x, y, z = p[:, 0], p[:, 1], p[:, 2]
         return torch.stack([(x * c + y * -s) + z * zero, (x * s + y * c) + z * zero, (x * zero + y * zero) + z * one], 1)
     out.vertices = (rotate(v) + centre[seg]).float().contiguous()               # step 6
-    shift = torch.from_numpy(np.repeat(obj_off[:-1], n_f)).to(dev)
+    face_obj = ragged.owners(n_f)
+    shift = torch.from_numpy(obj_off[face_obj]).to(dev)
     out.faces = (torch.cat([f.to(dev, torch.int64) for f, n in zip(faces, n_f) if n]) + shift[:, None]).to(torch.int32) \
         if face_off[-1] else torch.zeros(0, 3, dtype=torch.int32, device=dev)
-    out.face_obj = i32(np.repeat(np.arange(K), n_f))
+    out.face_obj = ragged.to_int32(face_obj, dev)
     if with_normals:
         n = torch.cat([as_t(m.vertex_normals).reshape(-1, 3).to(dev, torch.float64) for m, k in zip(meshes, n_v) if k])
         n = n @ torch.tensor(TRANSFORM_SHAPENET, dtype=torch.float64, device=dev).t()
