@@ -7,7 +7,8 @@ write the reference's output files.
   python demo.py --synthetic 10 --out out/synth --upsampling_steps 1
   python demo.py --synthetic 10 --out out/synth --with_normals     (PLYs with per-vertex nx ny nz)
   python demo.py --synthetic 10 --out out/synth --refinement_step 30   (meshes refined against the occupancy field)
-  python demo.py --synthetic 10 --out out/synth --render --post_processing   (scene_objects.ply and pred.png as well)
+  python demo.py --synthetic 10 --out out/synth --decimate_cells 16    (meshes thinned by vertex clustering, 16^3 cells)
+  python demo.py --synthetic 10 --out out/synth --render --post_processing  (scene_objects.ply and pred.png as well)
 
 Weights: --weight <pretrained_weight.pth> (reference checkpoint, key names kept);
 without it seeded random weights are used (no pretrained weights ship with the
@@ -54,6 +55,9 @@ def build_parser():
     ap.add_argument("--refinement_step", type=int, default=None,
                     help="RMSprop steps of Generator3D.refine_mesh on every mesh (generation.refinement_step; the "
                          "reference's configs use 0 or 30)")
+    ap.add_argument("--decimate_cells", type=int, default=None,
+                    help="thin every mesh by vertex clustering on an N^3 grid over its cube before normals and "
+                         "refinement (Generator3D.set_decimation; generation.decimate_cells, 0 = off)")
     ap.add_argument("--render", action="store_true",
                     help="place every mesh in its box (iscnet.scene.place_objects), render scan and meshes on the device "
                          "and write scene_objects.ply and pred.png beside the other files (demo.py:329-377; needs "
@@ -73,7 +77,8 @@ def main():
     from rfdnet_amd.iscnet.network import ISCNet
 
     gen = {k: v for k, v in (('resolution_0', args.resolution_0), ('upsampling_steps', args.upsampling_steps),
-                             ('refinement_step', args.refinement_step)) if v is not None}
+                             ('refinement_step', args.refinement_step), ('decimate_cells', args.decimate_cells))
+           if v is not None}
     if args.with_normals:
         gen['with_normals'] = True
     if args.config:

@@ -88,6 +88,7 @@ class Generator3D(object):
         self.stats = {}
         self.last_normals = None        # with_normals: the (V,3) f32 normals of the last extract_meshes(), all meshes
         self.refine_eps_source, self.refine_seed = 'numpy', None       # set_refinement()
+        self.decimate_cells = 0         # set_decimation()
         self._round0_cache = _lib.ArtefactCache(64)     # made here: the worker views of one network share it
 
     def set_refinement(self, steps, eps_source='numpy', seed=None):
@@ -104,6 +105,17 @@ class Generator3D(object):
         if eps_source not in ('numpy', 'device'):
             raise ValueError("eps_source must be 'numpy' or 'device'")
         self.refinement_step, self.refine_eps_source, self.refine_seed = steps, eps_source, seed
+        return self
+
+    def set_decimation(self, cells):
+        """Thin every extracted mesh by vertex clustering on a `cells`^3 grid over the generator's cube (decimate.py), between
+        marching cubes and the normals / the refinement: where the reference calls simplify_mesh (generator.py:189-191).
+        0 or None = off (the default).  Not the reference's algorithm: its sequential edge collapse stays unsupported
+        (simplify_nfaces raises)."""
+        cells = int(cells or 0)
+        if cells < 0:
+            raise ValueError("decimation cells must be >= 0")
+        self.decimate_cells = cells
         return self
 
     def _needs_fold(self):
@@ -261,7 +273,9 @@ class Generator3D(object):
     def extract_meshes(self, grids, fold=None):
         """fold = (table, fc_p_w) of the codes the grids came from: vertex normals from the decoder's gradient
         (Generator3D.estimate_normals), one launch for all meshes; with set_refinement(), the refinement of all meshes
-        (refine_meshes) -- after the normals, which belong to the unrefined vertices as in the reference (generator.py:173-195)"""
+        (refine_meshes) -- after the normals, which belong to the unrefined vertices as in the reference (generator.py:173-195).
+        With set_decimation() the meshes are thinned first: normals, refinement, last_buffers and the Mesh list are those of
+        the decimated meshes."""
         from .mcubes import marching_cubes_batch
         thr = self.logit_threshold()
         n = grids.shape[1]
@@ -275,6 +289,11 @@ class Generator3D(object):
         a = box_size / (n - 1)
         v, f, vend, tend = marching_cubes_batch(grids, thr, pad_value=-1e6, return_flat=True,
                                                 affine=(a, -1.5 * a - 0.5 * box_size))
+        if self.decimate_cells:
+            from .decimate import decimate_meshes
+            K = len(vend) - 1
+            v, f, vend, tend = decimate_meshes(v, f, vend, tend, self.decimate_cells, lo=np.full((K, 3), -box_size / 2),
+                                               h=np.full(K, box_size / self.decimate_cells))
         self.last_normals = None
         refine = self.refinement_step > 0
         if refine and fold is None:
@@ -282,7 +301,9 @@ class Generator3D(object):
         nrm = None
         if fold is not None and (self.with_normals or not refine):
             # generator.py:173-176: normals of every non-empty mesh; the reference leaves them None on an empty one
-            nrm = self.last_normals = self.model.decoder.normals(v, vend, fold[0], fold[1])
+            # (decimated vertices are f32; the normals kernel reads f64: widened, exact)
+            nrm = self.last_normals = self.model.decoder.normals(v if v.dtype == torch.float64 else v.double(), vend,
+                                                                 fold[0], fold[1])
         if refine:
             v = self.refine_meshes(v, f, vend, tend, fold, self.refinement_step)
         self.last_buffers = (v, f, vend, tend)

@@ -41,6 +41,22 @@ def timed(fn, reps, warmup):
     return {"ms": statistics.median(ms), "ms_min": min(ms), "ms_max": max(ms)}
 
 
+def placement_draws(rng, n_obj):
+    """the two draws that place a box used again (centre offsets, heading noise); the objects' dents are drawn after them"""
+    return rng.uniform(-1.5, 1.5, (n_obj, 3)), rng.normal(0, 0.3, n_obj)
+
+
+def object_grids(rng, n_obj):
+    """(n_obj, GRID, GRID, GRID) f32 value grids on the GPU: a sphere with a few dents of its own per object"""
+    g = np.stack(np.meshgrid(*[np.arange(GRID, dtype=np.float32)] * 3, indexing='ij'), -1) - (GRID - 1) / 2.
+    r = np.linalg.norm(g, axis=-1)
+    grids = torch.empty(n_obj, GRID, GRID, GRID, device="cuda")
+    for k in range(n_obj):
+        w = rng.normal(0, 1, 3)
+        grids[k] = torch.from_numpy((0.45 * GRID - r + 1.5 * np.sin(g @ w / 4.)).astype(np.float32))
+    return grids
+
+
 def scene_inputs(n_obj, points=80000):
     from rfdnet_amd import synthetic
     from rfdnet_amd.iscnet import box_util
@@ -49,16 +65,12 @@ def scene_inputs(n_obj, points=80000):
     rng = np.random.default_rng(5)
     again = np.arange(n_obj) >= len(boxes)                                       # a box used again: somewhere else
     boxes = boxes[np.arange(n_obj) % len(boxes)].astype(np.float64)
-    centre = boxes[:, :3] + again[:, None] * rng.uniform(-1.5, 1.5, (n_obj, 3)) * (1., 1., 0.)
-    heading = boxes[:, 6] + rng.normal(0, 0.3, n_obj)
+    offset, noise = placement_draws(rng, n_obj)
+    centre = boxes[:, :3] + again[:, None] * offset * (1., 1., 0.)
+    heading = boxes[:, 6] + noise
     corners = box_util.box_corners_upright_camera(torch.from_numpy(centre), torch.from_numpy(boxes[:, 3:6]),
                                                   torch.from_numpy(heading))[None].cuda()
-    g = np.stack(np.meshgrid(*[np.arange(GRID, dtype=np.float32)] * 3, indexing='ij'), -1) - (GRID - 1) / 2.
-    r = np.linalg.norm(g, axis=-1)
-    grids = torch.empty(n_obj, GRID, GRID, GRID, device="cuda")
-    for k in range(n_obj):                                                       # a sphere with a few dents of its own
-        w = rng.normal(0, 1, 3)
-        grids[k] = torch.from_numpy((0.45 * GRID - r + 1.5 * np.sin(g @ w / 4.)).astype(np.float32))
+    grids = object_grids(rng, n_obj)
     meshes = [types.SimpleNamespace(vertices=v, faces=f) for v, f in marching_cubes_batch(grids, 0.)]
     parsed = {'pred_corners_3d_upright_camera': corners,
               'pred_sem_cls': torch.from_numpy(rng.integers(0, 18, (1, n_obj))).cuda()}
