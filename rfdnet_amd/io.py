@@ -2,6 +2,9 @@
 
   read_off            the scan format of demo/inputs/*.off (trimesh.load(...).vertices,
                       demo.py:25)
+  write_off           the format of the watertight CAD meshes (mcubes.export_off in
+                      utils/shapenet/1_fuse_shapenetv2.py); read_off reads it back
+  read_obj            ShapeNet's model_normalized.obj: `v` and `f` records
   load_demo_data      demo.py:24-48: vertices -> [xyz | height] -> random_sampling
                       (utils/pc_util.py:35-47) -> (1, N, 4) float32 tensor
   write_mesh_ply      `proposal_%d_mesh.ply` as trimesh exports it (binary
@@ -63,6 +66,46 @@ def read_off(path):
         p += 1 + k
         # optional per-face colour values are not consumed (unused on this path)
     return v, faces
+
+
+def write_off(path, vertices, faces):
+    """vertices (V,3), faces (F,k) or a list of index lists -> an 'OFF' file that read_off reads back (17 significant
+    digits: a float64 survives the round trip)"""
+    v = np.asarray(vertices, dtype=np.float64).reshape(-1, 3)
+    faces = [[int(i) for i in f] for f in (faces.tolist() if hasattr(faces, "tolist") else faces)]
+    lines = ["OFF", "%d %d 0" % (v.shape[0], len(faces))]
+    lines += ["%.17g %.17g %.17g" % (p[0], p[1], p[2]) for p in v]
+    lines += [" ".join(str(i) for i in [len(f)] + f) for f in faces]
+    with open(path, "w") as fh:
+        fh.write("\n".join(lines) + "\n")
+
+
+def read_obj(path):
+    """-> (vertices (V,3) float64, faces (F,3) int32) of a Wavefront OBJ: `v` and `f` records only (the reference reads
+    ShapeNet's models with flags=('v', 'f')); a face token may be a, a/b, a//c or a/b/c (the vertex index counts), a
+    polygon is fanned into triangles from its first corner.  A negative (relative) or out-of-range index is refused."""
+    vertices, faces = [], []
+    with open(path, "r") as fh:
+        for number, line in enumerate(fh, 1):
+            rec = line.split("#", 1)[0].split()
+            if not rec:
+                continue
+            if rec[0] == "v":
+                if len(rec) < 4:
+                    raise ValueError("%s:%d: a vertex has three coordinates" % (path, number))
+                vertices.append([float(t) for t in rec[1:4]])
+            elif rec[0] == "f":
+                idx = [int(t.split("/")[0]) for t in rec[1:]]
+                if len(idx) < 3:
+                    raise ValueError("%s:%d: a face has at least three corners" % (path, number))
+                if min(idx) < 1:
+                    raise ValueError("%s:%d: negative (relative) and zero indices are not supported" % (path, number))
+                faces += [[idx[0] - 1, idx[k] - 1, idx[k + 1] - 1] for k in range(1, len(idx) - 1)]
+    v = np.asarray(vertices, dtype=np.float64).reshape(-1, 3)
+    f = np.asarray(faces, dtype=np.int64).reshape(-1, 3)
+    if f.size and f.max() >= v.shape[0]:
+        raise ValueError("%s: a face names vertex %d of %d" % (path, f.max() + 1, v.shape[0]))
+    return v, f.astype(np.int32)
 
 
 def random_sampling(pc, num_sample, rng, replace=None):

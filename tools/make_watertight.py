@@ -1,0 +1,71 @@
+"""A watertight mesh from any triangle soup, on one GPU (rfdnet_amd.watertight: the reference's
+utils/shapenet/1_fuse_shapenetv2.py, and with --decimate_cells the place of its 3_simplify_fusion.py).
+
+    python tools/make_watertight.py IN.{off,obj,ply} OUT.off [--resolution 256] [--views 200] [--image_size 640]
+                                    [--decimate_cells N]
+
+The focal length is the image size, as in the reference (640 at 640 x 640).  --decimate_cells N thins the result with the
+device decimation (rfdnet_amd.iscnet.decimate) on a grid of N^3 cells over the mesh's bounding cube.  Prints one JSON
+line: the counts of what was read and what was written."""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+
+def read_mesh(path):
+    from rfdnet_amd import io
+    ext = os.path.splitext(path)[1].lower()
+    if ext == ".off":
+        v, faces = io.read_off(path)
+        tris = [[f[0], f[k], f[k + 1]] for f in faces for k in range(1, len(f) - 1)]      # polygons as fans
+        return v[:, :3], np.asarray(tris, np.int32).reshape(-1, 3)
+    if ext == ".obj":
+        return io.read_obj(path)
+    if ext == ".ply":
+        v, f = io.read_mesh_ply(path)
+        return v.astype(np.float64), f.astype(np.int32)
+    raise SystemExit("make_watertight reads .off, .obj and .ply, not %s" % path)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("input")
+    ap.add_argument("output")
+    ap.add_argument("--resolution", type=int, default=256)
+    ap.add_argument("--views", type=int, default=200)
+    ap.add_argument("--image_size", type=int, default=640)
+    ap.add_argument("--decimate_cells", type=int, default=0)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("make_watertight runs on a GPU: none is visible")
+    from rfdnet_amd import io
+    from rfdnet_amd.watertight import watertight
+    v, f = read_mesh(args.input)
+    if not len(v) or not len(f):
+        raise SystemExit("%s holds no triangles" % args.input)
+    dev = torch.device("cuda")
+    vt, ft = watertight(torch.from_numpy(v).to(dev), torch.from_numpy(f).to(dev), resolution=args.resolution,
+                        n_views=args.views, image_size=args.image_size, focal=float(args.image_size))
+    result = {"tool": "make_watertight", "input": {"vertices": int(len(v)), "faces": int(len(f))},
+              "watertight": {"vertices": int(vt.shape[0]), "faces": int(ft.shape[0])}}
+    if args.decimate_cells and ft.shape[0]:
+        from rfdnet_amd.iscnet.decimate import decimate_meshes
+        lo, hi = vt.amin(0).cpu().numpy(), vt.amax(0).cpu().numpy()
+        side = float((hi - lo).max()) * (1 + 1e-6)                     # the highest vertex stays inside the last cell
+        vt, ft, _, _ = decimate_meshes(vt, ft, [0, vt.shape[0]], [0, ft.shape[0]], args.decimate_cells,
+                                       lo=(lo + hi) / 2 - side / 2, h=side / args.decimate_cells)
+        result["decimated"] = {"cells": args.decimate_cells, "vertices": int(vt.shape[0]), "faces": int(ft.shape[0])}
+    io.write_off(args.output, vt.double().cpu().numpy(), ft.cpu().numpy())
+    print(json.dumps(result))
+
+
+if __name__ == "__main__":
+    main()
