@@ -15,9 +15,10 @@ _f = C.c_void_p      # device pointers travel as integers (tensor.data_ptr())
 _i = C.c_int
 _fl = C.c_float
 _sz = C.c_size_t
+_d = C.c_double
 
 # name -> (restype, argtypes[, OPTIONAL]): exactly the prototypes of include/rfd_pointnet2.h / rfd_occ.h /
-# rfd_chamfer.h / rfd_eval.h / rfd_latent.h / rfd_loss.h / rfd_fit.h / rfd_render.h / rfd_decimate.h / rfd_fuse.h.  OPTIONAL marks the test hooks, which a deployment build (RFD_NO_TEST_HOOKS=1, build.py)
+# rfd_chamfer.h / rfd_eval.h / rfd_latent.h / rfd_loss.h / rfd_fit.h / rfd_render.h / rfd_decimate.h / rfd_fuse.h / rfd_sample.h.  OPTIONAL marks the test hooks, which a deployment build (RFD_NO_TEST_HOOKS=1, build.py)
 # leaves out.
 OPTIONAL = "optional"
 ABI = {
@@ -108,6 +109,12 @@ ABI = {
     "rfd_decimate_compact_faces": (_i, [_i, _i, _f, _f, _f, _f, _f, _f, _f, _f]),
     "rfd_depth_from_keys": (_i, [_i, _i, _f, _fl, _fl, _f, _f]),
     "rfd_tsdf_fuse": (_i, [_i, _i, _i, _f, _f, _f, _f, _i, _i, _i, _fl, _fl, _i, _fl, _i, _f, _f, _f]),
+    "rfd_sample_rescale": (_i, [_i, _f, _d, _d, _d, _d, _d, _d, _i, _f, _f, _f]),
+    "rfd_sample_cells": (_i, [_i, _f, _i, _f, _f, _f]),
+    "rfd_sample_contains": (_i, [_i, _f, _d, _d, _d, _d, _d, _d, _i, _i, _f, _f, _f, _f, _f, _f, _f]),
+    "rfd_sample_voxelize": (_i, [_i, _f, _i, _f, _f]),
+    "rfd_sample_face_areas": (_i, [_i, _f, _f, _f]),
+    "rfd_sample_surface": (_i, [_i, _i, _f, _f, _f, _f, _f, _f, _f]),
     "rfd_last_error_string": (C.c_char_p, []),
     "rfd_build_arch": (C.c_char_p, []),
     "rfd_device_status": (_i, []),

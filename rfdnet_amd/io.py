@@ -5,6 +5,9 @@
   write_off           the format of the watertight CAD meshes (mcubes.export_off in
                       utils/shapenet/1_fuse_shapenetv2.py); read_off reads it back
   read_obj            ShapeNet's model_normalized.obj: `v` and `f` records
+  write_binvox        `#binvox 1` voxel grids as the reference's external/binvox_rw.py writes them
+  read_binvox         (axis order xyz, run-length pairs); write_points_npz / write_pointcloud_npz:
+                      points.npz and pointcloud.npz of utils/shapenet/2_sample_mesh.py
   load_demo_data      demo.py:24-48: vertices -> [xyz | height] -> random_sampling
                       (utils/pc_util.py:35-47) -> (1, N, 4) float32 tensor
   write_mesh_ply      `proposal_%d_mesh.ply` as trimesh exports it (binary
@@ -106,6 +109,65 @@ def read_obj(path):
     if f.size and f.max() >= v.shape[0]:
         raise ValueError("%s: a face names vertex %d of %d" % (path, f.max() + 1, v.shape[0]))
     return v, f.astype(np.int32)
+
+
+def write_binvox(path, voxels, translate, scale):
+    """voxels (R,R,R) bool indexed [x, y, z] -> a '#binvox 1' file as the reference's binvox_rw writes it for
+    axis_order='xyz': the file's own order is x, z, y (y fastest), run-length pairs (value, count) with count <= 255.
+    Byte for byte binvox_rw's, including its one quirk: a run whose length is a multiple of 255 and that is not the last
+    ends with a pair of count 0 (which every reader skips)."""
+    v = np.asarray(voxels)
+    if v.ndim != 3 or v.size == 0:
+        raise ValueError("write_binvox: a non-empty (X,Y,Z) grid, got %s" % (v.shape,))
+    flat = np.transpose(v.astype(bool), (0, 2, 1)).reshape(-1).astype(np.uint8)
+    start = np.concatenate([[0], np.nonzero(np.diff(flat))[0] + 1])
+    length = np.diff(np.concatenate([start, [flat.size]]))
+    pairs = bytearray()
+    for i, (value, n) in enumerate(zip(flat[start].tolist(), length.tolist())):
+        pairs += bytes([value, 255]) * (n // 255)
+        if n % 255 or i + 1 < len(start):
+            pairs += bytes([value, n % 255])
+    head = "#binvox 1\ndim %s\ntranslate %s\nscale %s\ndata\n" % (
+        " ".join(str(int(d)) for d in v.shape), " ".join(str(float(t)) for t in np.asarray(translate).reshape(-1)),
+        str(float(scale)))
+    with open(path, "wb") as fh:
+        fh.write(head.encode("ascii") + bytes(pairs))
+
+
+def read_binvox(path):
+    """-> (voxels (X,Y,Z) bool indexed [x, y, z], translate (3,) float64, scale float) of a '#binvox 1' file"""
+    with open(path, "rb") as fh:
+        if not fh.readline().strip().startswith(b"#binvox"):
+            raise ValueError("not a binvox file: %s" % path)
+        dims = [int(t) for t in fh.readline().split()[1:]]
+        translate = np.array([float(t) for t in fh.readline().split()[1:]], np.float64)
+        scale = float(fh.readline().split()[1])
+        fh.readline()
+        raw = np.frombuffer(fh.read(), np.uint8)
+    flat = np.repeat(raw[::2], raw[1::2]).astype(bool)
+    if len(dims) != 3 or flat.size != int(np.prod(dims)):
+        raise ValueError("%s: %d voxels in the runs, dim %s" % (path, flat.size, dims))
+    return np.transpose(flat.reshape(dims[0], dims[2], dims[1]), (0, 2, 1)).copy(), translate, scale
+
+
+def _npz_arrays(points, loc, scale, float16):
+    return (np.asarray(points).astype(np.float16 if float16 else np.float32), np.asarray(loc, np.float64),
+            np.float64(scale))
+
+
+def write_points_npz(path, points, occupancies, loc, scale, float16=False, packbits=False):
+    """The reference's points.npz (export_points): points (n,3) f32 or f16, occupancies (n,) bool or, with packbits,
+    the uint8 of np.packbits, loc (3,), scale"""
+    points, loc, scale = _npz_arrays(points, loc, scale, float16)
+    occ = np.asarray(occupancies).astype(bool)
+    np.savez(path, points=points, occupancies=np.packbits(occ) if packbits else occ, loc=loc, scale=scale)
+
+
+def write_pointcloud_npz(path, points, normals, loc, scale, float16=False, packbits=False):
+    """The reference's pointcloud.npz (export_pointcloud): points and normals (n,3) f32 or f16, loc (3,), scale.  There is
+    nothing boolean in it: packbits is accepted for symmetry with write_points_npz and changes nothing."""
+    points, loc, scale = _npz_arrays(points, loc, scale, float16)
+    np.savez(path, points=points, normals=np.asarray(normals).astype(points.dtype), loc=loc, scale=scale)
 
 
 def random_sampling(pc, num_sample, rng, replace=None):
