@@ -268,6 +268,15 @@ def as_tensor(a, device, dtype):
     return (a if torch.is_tensor(a) else torch.as_tensor(np.asarray(a))).to(device, dtype)
 
 
+def need_gpu(*tensors):
+    """The one guard of the host modules: RuntimeError("CPU not supported") (the reference's wording, sampling.cpp:34 et
+    al.) unless every argument is a tensor on a CUDA device.  None is refused too: pass only what the call requires."""
+    import torch
+    for t in tensors:
+        if not (torch.is_tensor(t) and t.is_cuda):
+            raise RuntimeError("CPU not supported")
+
+
 def call(name, device, *args):
     """The one way a host module launches: ABI entry `name` (one whose last C parameter is the stream) with `args` and
     the current stream of `device`, on that device; a non-zero return raises, naming `name`."""

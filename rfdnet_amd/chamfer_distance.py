@@ -12,8 +12,7 @@ from . import _lib
 class ChamferDistanceFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, xyz1, xyz2):
-        if not (xyz1.is_cuda and xyz2.is_cuda):
-            raise RuntimeError("CPU not supported")
+        _lib.need_gpu(xyz1, xyz2)
         xyz1 = xyz1.contiguous().float()
         xyz2 = xyz2.contiguous().float()
         b, n, _ = xyz1.size()

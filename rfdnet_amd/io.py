@@ -5,6 +5,7 @@
   write_off           the format of the watertight CAD meshes (mcubes.export_off in
                       utils/shapenet/1_fuse_shapenetv2.py); read_off reads it back
   read_obj            ShapeNet's model_normalized.obj: `v` and `f` records
+  read_mesh           "a mesh file" of the mesh tools: .off, .obj or .ply -> float64 vertices, int32 triangles
   write_binvox        `#binvox 1` voxel grids as the reference's external/binvox_rw.py writes them
   read_binvox         (axis order xyz, run-length pairs); write_points_npz / write_pointcloud_npz:
                       points.npz and pointcloud.npz of utils/shapenet/2_sample_mesh.py
@@ -231,6 +232,22 @@ def read_mesh_ply(path, return_normals=False):
     if return_normals:
         return v, f, (vn[:, 3:].copy() if has_n else None)
     return v, f
+
+
+def read_mesh(path):
+    """a mesh file by its extension -> (vertices (V,3) float64, faces (F,3) int32): .off (colour columns dropped,
+    polygons fanned from their first corner), .obj (read_obj) or .ply (read_mesh_ply, widened); else ValueError"""
+    ext = os.path.splitext(path)[1].lower()
+    if ext == ".off":
+        v, faces = read_off(path)
+        tris = [[f[0], f[k], f[k + 1]] for f in faces for k in range(1, len(f) - 1)]
+        return v[:, :3], np.asarray(tris, np.int32).reshape(-1, 3)
+    if ext == ".obj":
+        return read_obj(path)
+    if ext == ".ply":
+        v, f = read_mesh_ply(path)
+        return v.astype(np.float64), f.astype(np.int32)
+    raise ValueError("%s: a mesh file is .off, .obj or .ply" % path)
 
 
 def write_points_ply(path, points):

@@ -47,8 +47,7 @@ def decimate_meshes(v, f, vend, tend, cells, lo=None, h=None, regularise=REGULAR
         raise ValueError("cells must be >= 1, not %d" % cells)
     if K * cells ** 3 >= ragged.INT32_END:
         raise ValueError("%d meshes of %d^3 cells: the keys must stay below 2^31 (int32)" % (K, cells))
-    if not (torch.is_tensor(v) and torch.is_tensor(f) and v.is_cuda and f.is_cuda):
-        raise RuntimeError("CPU not supported")
+    _lib.need_gpu(v, f)
     if v.dtype not in (torch.float64, torch.float32):
         raise TypeError("vertices must be float64 or float32, not %s" % v.dtype)
     if lo is None or h is None:

@@ -66,8 +66,7 @@ class Encoder_Latent(nn.Module):
     def posterior(self, p, x, c=None, eps=None):
         """p (K,T,3), x (K,T) occupancies, c (K,c_dim) -> (mean, logstd, z, kl); z = mean + exp(logstd) eps and
         kl (K,) = KL(q || N(0,1)) summed over z_dim come out of the head kernel when eps (K,z_dim) is given, else None."""
-        if not p.is_cuda:
-            raise RuntimeError("CPU not supported")
+        _lib.need_gpu(p)
         K, T, _ = p.shape
         dev = p.device
         p = p.detach().contiguous().float()

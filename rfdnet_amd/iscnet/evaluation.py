@@ -391,8 +391,7 @@ def voxel_iou(logits, logit_threshold, gt_voxels, return_counts=False):
     """compute_iou (net_utils/libs.py) of the predicted voxels `logits >= logit_threshold` against `gt_voxels >= 0.5`:
     logits (K,V) or (K,n,n,n) f32, gt_voxels the same shape (any dtype) -> iou (K,) f32 on the device =
     inter.float() / union.float() from one rfd_voxel_iou launch; NaN for an empty pair, as numpy's 0 / 0."""
-    if not logits.is_cuda:
-        raise RuntimeError("CPU not supported")
+    _lib.need_gpu(logits)
     K = logits.shape[0]
     logits, ld = _lib.rows(logits.reshape(K, -1).float())
     V = logits.shape[1]

@@ -34,12 +34,6 @@ def huber_loss(error, delta=1.0):
     return 0.5 * quadratic ** 2 + delta * linear
 
 
-def _need_cuda(t):
-    if not t.is_cuda:
-        raise RuntimeError("CPU not supported")
-    return t.device
-
-
 def _as(t, dtype, dev):
     """`t` on `dev`, contiguous, of `dtype`: no kernel when it already is (the dataloader's dtypes)"""
     return _lib.as_tensor(t, dev, dtype).contiguous()
@@ -59,7 +53,8 @@ def _strided(t):
 
 def _vote_partial(est_data, gt_data, partial):
     seed_xyz = est_data['seed_xyz']
-    dev = _need_cuda(seed_xyz)
+    _lib.need_gpu(seed_xyz)
+    dev = seed_xyz.device
     B, S = seed_xyz.shape[:2]
     vote_xyz = _as(est_data['vote_xyz'], torch.float32, dev)
     vote_factor = vote_xyz.shape[1] // max(S, 1)
@@ -83,7 +78,8 @@ def _mean_size(config, dev):
 
 def _proposal_partial(est_data, gt_data, config, partial, meta_data=None):
     agg = est_data['aggregated_vote_xyz']
-    dev = _need_cuda(agg)
+    _lib.need_gpu(agg)
+    dev = agg.device
     B, K = agg.shape[:2]
     agg = _as(agg, torch.float32, dev)
     center = _as(est_data['center'], torch.float32, dev)
@@ -138,7 +134,8 @@ def _partials(B, dev):
 @torch.no_grad()
 def compute_vote_loss(est_data, gt_data):
     """-> vote_loss, a 0-d device tensor (models/loss.py:41-88)"""
-    dev = _need_cuda(est_data['seed_xyz'])
+    _lib.need_gpu(est_data['seed_xyz'])
+    dev = est_data['seed_xyz'].device
     B = est_data['seed_xyz'].shape[0]
     partial = _partials(B, dev)
     _vote_partial(est_data, gt_data, partial)
@@ -150,7 +147,8 @@ def compute_objectness_loss(est_data, gt_data, config=None):
     """-> objectness_loss (0-d), objectness_label (B,K) int64, objectness_mask (B,K) f32, object_assignment (B,K) int64
     (models/loss.py:90-129).  config: the dataset config (default: ScanNet's) -- the proposal kernel computes the box
     terms in the same pass."""
-    dev = _need_cuda(est_data['aggregated_vote_xyz'])
+    _lib.need_gpu(est_data['aggregated_vote_xyz'])
+    dev = est_data['aggregated_vote_xyz'].device
     B, K = est_data['aggregated_vote_xyz'].shape[:2]
     if config is None:
         config = _default_config()
@@ -173,7 +171,8 @@ def _default_config():
 def compute_box_and_sem_cls_loss(est_data, gt_data, meta_data, config):
     """-> center_loss, heading_cls_loss, heading_reg_loss, size_cls_loss, size_reg_loss, sem_cls_loss (0-d device
     tensors) at meta_data's object_assignment / objectness_label (models/loss.py:131-202)"""
-    dev = _need_cuda(est_data['center'])
+    _lib.need_gpu(est_data['center'])
+    dev = est_data['center'].device
     B, K = est_data['center'].shape[:2]
     partial = _partials(B, dev)
     _proposal_partial(est_data, gt_data, config, partial, meta_data)
@@ -204,7 +203,8 @@ class DetectionLoss(BaseLoss):
     @torch.no_grad()
     def __call__(self, est_data, gt_data, dataset_config):
         """-> the reference's dictionary: 'total' a 0-d device tensor, the twelve other keys Python floats"""
-        dev = _need_cuda(est_data['seed_xyz'])
+        _lib.need_gpu(est_data['seed_xyz'])
+        dev = est_data['seed_xyz'].device
         B, K = est_data['aggregated_vote_xyz'].shape[:2]
         partial = _partials(B, dev)
         _vote_partial(est_data, gt_data, partial)

@@ -142,8 +142,7 @@ class DecoderCBatchNorm(nn.Module):
         def build():
             sd = {k: v.detach() for k, v in self.state_dict().items()}
             fc0, fc1 = occ_fold.stacked_fc_weights(sd)
-            if not fc0.is_cuda:
-                raise RuntimeError("CPU not supported")
+            _lib.need_gpu(fc0)
             if bwd:
                 fc0, fc1 = (fc1.flip(0).transpose(1, 2).contiguous(),      # W1^T of blocks 4 .. 0
                             fc0.flip(0).transpose(1, 2).contiguous())      # W0^T of blocks 4 .. 0
@@ -287,8 +286,7 @@ class DecoderCBatchNorm(nn.Module):
         dL/dp = dL/dlogit * d logit / d p through the normals kernel (csrc/occ_normals.hip) -- what the reference's
         Generator3D.estimate_normals needs (vi.requires_grad_(); decode(vi).logits.sum().backward(); -vi.grad).  That is
         the ONLY gradient this module has: none for z, c (an error if either requires grad) and none for the parameters."""
-        if not p.is_cuda:
-            raise RuntimeError("CPU not supported")
+        _lib.need_gpu(p)
         if torch.is_grad_enabled() and p.requires_grad:
             if z.requires_grad or c.requires_grad:
                 raise NotImplementedError("DecoderCBatchNorm: only the gradient with respect to the query points p is "

@@ -6,6 +6,7 @@ import torch
 import torch.distributions as dist
 import torch.nn as nn
 
+from .. import _lib
 from .generator import Generator3D
 from .occ_decoder import DecoderCBatchNorm, logit_threshold
 from .registers import MODULES
@@ -96,8 +97,7 @@ class ONet(nn.Module):
         if self.z_dim > 0 and self.encoder_latent is None:
             raise RuntimeError("ONet.compute_loss needs the latent encoder (z_dim = %d): call enable_latent_encoder() "
                                "(or set data.latent_encoder) and load its weights" % self.z_dim)
-        if not (feat.is_cuda and p.is_cuda and occ.is_cuda):
-            raise RuntimeError("CPU not supported")
+        _lib.need_gpu(feat, p, occ)
         device = feat.device
         K = feat.size(0)
         if self.use_cls_for_completion:
@@ -155,9 +155,7 @@ class ONet(nn.Module):
 def bce_logits_rowsum(logits, target):
     """(K,T) f32 device tensors (unit stride along T) -> (K,) f32: sum_t binary_cross_entropy_with_logits, one
     rfd_bce_logits_rowsum launch (f64 row sums in a fixed order: deterministic)"""
-    from .. import _lib
-    if not (logits.is_cuda and target.is_cuda):
-        raise RuntimeError("CPU not supported")
+    _lib.need_gpu(logits, target)
     K, T = logits.shape
     assert target.shape == (K, T) and logits.dtype == torch.float32 and target.dtype == torch.float32
     (logits, ld_l), (target, ld_t) = _lib.rows(logits), _lib.rows(target)

@@ -5,6 +5,8 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
+from .. import _lib
+
 
 class _TNet(nn.Module):
     """Shared trunk of STN3d (:7-42) and STNkd (:45-79): k_in -> k_out*k_out."""
@@ -140,9 +142,7 @@ def mask_loss_rows(logp, grouped_labels, proposal_labels, trans_feat, scale=0.00
     nll_loss(logp, grouped_labels == proposal_labels) + scale * feature_transform_reguliarzer(trans_feat), a 0-d tensor.
     logp (Kp,P,2) f32 log-probabilities, grouped_labels (Kp,P) the instance label of every grouped point (a row-strided
     view is read in place), proposal_labels (Kp,) the proposals' instance labels, trans_feat (Kp,64,64)."""
-    from .. import _lib
-    if not logp.is_cuda:
-        raise RuntimeError("CPU not supported")
+    _lib.need_gpu(logp)
     dev = logp.device
     Kp, P, k = logp.shape
     assert k == 2 and trans_feat.shape == (Kp, 64, 64) and grouped_labels.shape == (Kp, P)
@@ -169,8 +169,7 @@ class get_loss(nn.Module):
     def forward(self, pred, target, trans_feat, weight):
         if weight is not None:
             raise NotImplementedError("get_loss: class weights are not supported (the reference passes None)")
-        if not pred.is_cuda:
-            raise RuntimeError("CPU not supported")
+        _lib.need_gpu(pred)
         Kp = trans_feat.shape[0]
         P = pred.shape[0] // Kp
         assert pred.shape == (Kp * P, 2) and target.numel() == Kp * P

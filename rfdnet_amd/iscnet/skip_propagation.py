@@ -7,7 +7,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from .. import pos_embed
+from .. import _lib, pos_embed
 from ..pointnet2_ops.pointnet2_modules import STN_Group
 from .layers import ResnetPointnet
 from .pointseg import PointSeg, get_loss
@@ -39,8 +39,7 @@ class SkipPropagation(nn.Module):
         -- point_instance_labels (B,N), proposal_instance_labels (B,K) -- -> (object codes (B, c_dim, K), bit-identical
         to generate()'s; PointSeg's mask loss, a 0-d tensor: pointseg.mask_loss_rows on the grouped labels).  Values
         only, device tensors only."""
-        if not input_point_cloud.is_cuda:
-            raise RuntimeError("CPU not supported")
+        _lib.need_gpu(input_point_cloud)
         with torch.no_grad():
             return self._codes(box_xyz, box_orientations, box_feature, input_point_cloud,
                                (point_instance_labels, proposal_instance_labels))

@@ -7,10 +7,12 @@ query points with inside / outside labels, and a voxel grid.
   sample_surface                          trimesh's mesh.sample, by this project's own rules
   sample_points                           2_sample_mesh.py's export_points
   is_watertight                           every edge in exactly two faces
+  unit_cube                               2_sample_mesh.py's --resize: loc, scale and the moved vertices
 
 The kernels are csrc/mesh_sample.hip, the rules are written out in include/rfd_sample.h and restated in numpy in
 tests/mesh_sample_ref.py.  Containment and the surface voxels follow the reference's arithmetic operation by operation:
-they return its bits (tests/golden/F_SMP.npz).  Everything is queued on the current stream.  A mesh is checked BEFORE any
+they return its bits (tests/golden/F_SMP.npz).  unit_cube is the one copy of the tools' "move the mesh into the unit
+cube"; the GPU guard is _lib.need_gpu.  Everything is queued on the current stream.  A mesh is checked BEFORE any
 kernel or gather touches it (one read-back): an index outside the vertex array or a coordinate that is not finite is a
 ValueError here, never a fault on the device.
 """
@@ -23,10 +25,14 @@ MAX_HASH_RESOLUTION = 32768      # the cells are a flat int32 array
 MAX_VOXEL_RESOLUTION = 1024
 
 
-def _on_device(*tensors):
-    for t in tensors:
-        if not torch.is_tensor(t) or t.device.type != 'cuda':
-            raise RuntimeError("CPU not supported")
+def unit_cube(vertices):
+    """vertices (V,3) f64 on any device -> (vertices', loc (3,) f64, scale float): the mesh moved into the unit cube as
+    the sampling tools store it, loc = the centre of the bounding box, scale = its largest extent, vertices' =
+    (vertices - loc) * (1 / scale).  loc and scale go into every output file, so the arithmetic stays in this form: the
+    reciprocal, then the product (a division gives other bits).  One read-back, for scale."""
+    lo, hi = vertices.amin(0), vertices.amax(0)
+    loc, scale = (lo + hi) / 2, float((hi - lo).max())
+    return (vertices - loc) * (1 / scale), loc, scale
 
 
 def check_sizes(**sizes):
@@ -104,7 +110,7 @@ class MeshIntersector(object):
     @torch.no_grad()
     def __init__(self, vertices, faces, hash_resolution=512):
         self.resolution = res = check_hash_resolution(hash_resolution)
-        _on_device(vertices, faces)
+        _lib.need_gpu(vertices, faces)
         self.device = dev = vertices.device
         tri, lo, hi = mesh_triangles(vertices, faces)
         self.n_faces = F = int(tri.shape[0])
@@ -145,7 +151,7 @@ class MeshIntersector(object):
         below every point].  sort_points: walk the points in the order of their cells, so that a wave reads one list.  Off by
         default: on MI355X the sort costs more than the walk saves ("Occupancy samples"); the result is the
         same either way."""
-        _on_device(points)
+        _lib.need_gpu(points)
         if points.dtype not in (torch.float32, torch.float64) or points.dim() != 2 or points.shape[1] != 3:
             raise ValueError("query: points are (n,3) float32 or float64, got %s %s" % (points.dtype, tuple(points.shape)))
         n, dev = int(points.shape[0]), points.device
@@ -179,7 +185,7 @@ def check_mesh_contains(vertices, faces, points, hash_resolution=512):
 def voxelize_surface(vertices, faces, resolution):
     """-> (R,R,R) bool: the voxels of the cube [-0.5, 0.5]^3 that a triangle overlaps (the reference's voxelize_surface)"""
     R = check_voxel_resolution(resolution)
-    _on_device(vertices, faces)
+    _lib.need_gpu(vertices, faces)
     dev = vertices.device
     check_sizes(voxels=R ** 3)
     grid = torch.zeros(R, R, R, dtype=torch.uint8, device=dev)
@@ -205,13 +211,13 @@ def voxelize_interior(vertices, faces, resolution, jitter=None, generator=None):
     """-> (R,R,R) bool: is the (jittered) centre of every voxel inside the mesh.  jitter: (R^3,3) f64 on the device, or
     None: 0.1 (rand - 0.5) from `generator`, the reference's symmetry breaker."""
     R = check_voxel_resolution(resolution)
-    _on_device(vertices, faces)
+    _lib.need_gpu(vertices, faces)
     dev = vertices.device
     check_sizes(voxel_coordinates=3 * R ** 3)
     if jitter is None:
         jitter = 0.1 * (torch.rand(R ** 3, 3, dtype=torch.float64, device=dev, generator=generator) - 0.5)
     else:
-        _on_device(jitter)
+        _lib.need_gpu(jitter)
         if jitter.dtype != torch.float64 or tuple(jitter.shape) != (R ** 3, 3):
             raise ValueError("voxelize_interior: jitter is (%d,3) float64, got %s %s" % (R ** 3, jitter.dtype, tuple(jitter.shape)))
     return check_mesh_contains(vertices, faces, grid_points(R, jitter)).reshape(R, R, R)
@@ -230,7 +236,7 @@ def sample_surface(vertices, faces, count, u=None, generator=None, return_normal
     count = int(count)
     if count < 0:
         raise ValueError("sample_surface: count = %d" % count)
-    _on_device(vertices, faces)
+    _lib.need_gpu(vertices, faces)
     dev = vertices.device
     check_sizes(sample_coordinates=3 * count)
     points = torch.empty(count, 3, dtype=torch.float64, device=dev)
@@ -246,7 +252,7 @@ def sample_surface(vertices, faces, count, u=None, generator=None, return_normal
         if u is None:
             u = torch.rand(count, 3, dtype=torch.float64, device=dev, generator=generator)
         else:
-            _on_device(u)
+            _lib.need_gpu(u)
             if u.dtype != torch.float64 or tuple(u.shape) != (count, 3):
                 raise ValueError("sample_surface: u is (%d,3) float64, got %s %s" % (count, u.dtype, tuple(u.shape)))
             u = u.contiguous()
@@ -261,7 +267,7 @@ def sample_points(vertices, faces, size=100000, uniform_ratio=0.5, sigma=0.01, p
     """The reference's export_points -> points (size,3) f64, occupancies (size,) bool: int(size * uniform_ratio) points
     uniform in the cube of side 1 + padding, the rest on the surface plus sigma * randn, each labelled by
     check_mesh_contains.  (The cast to f32 / f16 and packbits belong to the tool that writes the file.)"""
-    _on_device(vertices, faces)
+    _lib.need_gpu(vertices, faces)
     dev = vertices.device
     n_uniform = int(size * uniform_ratio)
     n_surface = int(size) - n_uniform

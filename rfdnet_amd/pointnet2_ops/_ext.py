@@ -34,18 +34,13 @@ def _chk_cuda(x, name):
         raise RuntimeError("%s must be a CUDA tensor" % name)
 
 
-def _need_gpu(x):
-    if not x.is_cuda:
-        raise RuntimeError("CPU not supported")       # sampling.cpp:34 et al.
-
-
 def gather_points(points, idx):
     """(B,C,N) f32, (B,M) i32 -> (B,C,M).  sampling.cpp:15-38."""
     _chk_contig(points, "points"); _chk_contig(idx, "idx")
     _chk_float(points, "points"); _chk_int(idx, "idx")
     if points.is_cuda:
         _chk_cuda(idx, "idx")
-    _need_gpu(points)
+    _lib.need_gpu(points)
     B, Cc, N = points.shape
     M = idx.shape[1]
     out = torch.empty((B, Cc, M), dtype=torch.float32, device=points.device)
@@ -60,7 +55,7 @@ def gather_points_grad(grad_out, idx, n):
     _chk_float(grad_out, "grad_out"); _chk_int(idx, "idx")
     if grad_out.is_cuda:
         _chk_cuda(idx, "idx")
-    _need_gpu(grad_out)
+    _lib.need_gpu(grad_out)
     B, Cc, M = grad_out.shape
     out = torch.zeros((B, Cc, n), dtype=torch.float32, device=grad_out.device)
     _lib.call("gather_points_grad_kernel_wrapper", grad_out.device, B, Cc, n, M,
@@ -71,7 +66,7 @@ def gather_points_grad(grad_out, idx, n):
 def furthest_point_sampling(points, nsamples):
     """(B,N,3) f32 -> (B,nsamples) i32.  sampling.cpp:66-87."""
     _chk_contig(points, "points"); _chk_float(points, "points")
-    _need_gpu(points)
+    _lib.need_gpu(points)
     B, N = points.shape[0], points.shape[1]
     out = torch.zeros((B, nsamples), dtype=torch.int32, device=points.device)
     tmp = torch.empty((B, N), dtype=torch.float32, device=points.device)
@@ -86,7 +81,7 @@ def three_nn(unknowns, knows):
     _chk_float(unknowns, "unknowns"); _chk_float(knows, "knows")
     if unknowns.is_cuda:
         _chk_cuda(knows, "knows")
-    _need_gpu(unknowns)
+    _lib.need_gpu(unknowns)
     B, n = unknowns.shape[0], unknowns.shape[1]
     m = knows.shape[1]
     idx = torch.empty((B, n, 3), dtype=torch.int32, device=unknowns.device)
@@ -102,7 +97,7 @@ def three_interpolate(points, idx, weight):
     _chk_float(points, "points"); _chk_int(idx, "idx"); _chk_float(weight, "weight")
     if points.is_cuda:
         _chk_cuda(idx, "idx"); _chk_cuda(weight, "weight")
-    _need_gpu(points)
+    _lib.need_gpu(points)
     B, Cc, m = points.shape
     n = idx.shape[1]
     out = torch.empty((B, Cc, n), dtype=torch.float32, device=points.device)
@@ -117,7 +112,7 @@ def three_interpolate_grad(grad_out, idx, weight, m):
     _chk_float(grad_out, "grad_out"); _chk_int(idx, "idx"); _chk_float(weight, "weight")
     if grad_out.is_cuda:
         _chk_cuda(idx, "idx"); _chk_cuda(weight, "weight")
-    _need_gpu(grad_out)
+    _lib.need_gpu(grad_out)
     B, Cc, n = grad_out.shape
     out = torch.zeros((B, Cc, m), dtype=torch.float32, device=grad_out.device)
     _lib.call("three_interpolate_grad_kernel_wrapper", grad_out.device, B, Cc, n, m,
@@ -131,7 +126,7 @@ def ball_query(new_xyz, xyz, radius, nsample):
     _chk_float(new_xyz, "new_xyz"); _chk_float(xyz, "xyz")
     if new_xyz.is_cuda:
         _chk_cuda(xyz, "xyz")
-    _need_gpu(new_xyz)
+    _lib.need_gpu(new_xyz)
     B, N = xyz.shape[0], xyz.shape[1]
     M = new_xyz.shape[1]
     # the kernel writes every element (zeros for empty balls): no zero-fill pass
@@ -147,7 +142,7 @@ def group_points(points, idx):
     _chk_float(points, "points"); _chk_int(idx, "idx")
     if points.is_cuda:
         _chk_cuda(idx, "idx")
-    _need_gpu(points)
+    _lib.need_gpu(points)
     B, Cc, N = points.shape
     M, ns = idx.shape[1], idx.shape[2]
     out = torch.empty((B, Cc, M, ns), dtype=torch.float32, device=points.device)
@@ -162,7 +157,7 @@ def group_points_grad(grad_out, idx, n):
     _chk_float(grad_out, "grad_out"); _chk_int(idx, "idx")
     if grad_out.is_cuda:
         _chk_cuda(idx, "idx")
-    _need_gpu(grad_out)
+    _lib.need_gpu(grad_out)
     B, Cc, M, ns = grad_out.shape
     out = torch.zeros((B, Cc, n), dtype=torch.float32, device=grad_out.device)
     _lib.call("group_points_grad_kernel_wrapper", grad_out.device, B, Cc, n, M, ns,
@@ -175,7 +170,7 @@ def group_points_grad(grad_out, idx, n):
 def furthest_point_sampling_gather(points, nsamples):
     """FPS that also returns the sampled centres (B,nsamples,3)."""
     _chk_contig(points, "points"); _chk_float(points, "points")
-    _need_gpu(points)
+    _lib.need_gpu(points)
     B, N = points.shape[0], points.shape[1]
     out = torch.zeros((B, nsamples), dtype=torch.int32, device=points.device)
     new_xyz = torch.empty((B, nsamples, 3), dtype=torch.float32, device=points.device)
@@ -190,7 +185,7 @@ def group_concat(xyz, new_xyz, features, idx, radius, normalize_xyz, use_xyz,
     """QueryAndGroup epilogue in one pass (pointnet2_utils.py:333-344)."""
     _chk_contig(xyz, "xyz"); _chk_contig(new_xyz, "new_xyz"); _chk_contig(idx, "idx")
     _chk_float(xyz, "xyz"); _chk_float(new_xyz, "new_xyz"); _chk_int(idx, "idx")
-    _need_gpu(xyz)
+    _lib.need_gpu(xyz)
     B, N = xyz.shape[0], xyz.shape[1]
     M, ns = idx.shape[1], idx.shape[2]
     Cc = 0

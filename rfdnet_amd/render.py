@@ -3,6 +3,10 @@ meshes and boxes to VTK and saves pred.png).  Here the picture is rasterised on 
 (csrc/raster.hip; the rules are in include/rfd_render.h and restated in tests/render_f64.py): one clear and three
 launches per image, queued on the current stream, no host synchronisation.  Box wireframes, anti-aliasing and a
 pixel-for-pixel match of VTK's picture are not attempted.
+
+This module is the rasteriser's one host driver: camera_params() lays out the 16 doubles the library takes and
+rasterise() owns the scratch buffers and the projection and triangle launches.  render_scene() shades its keys into a
+picture; watertight.render_depthmaps() turns them into depth maps, one view after another on the same scratch.
 """
 import collections
 import ctypes
@@ -13,6 +17,7 @@ import torch
 from . import _lib
 
 RenderResult = collections.namedtuple("RenderResult", "image depth ids")
+RasterScratch = collections.namedtuple("RasterScratch", "q sxy valid keys")
 
 # one colour per semantic class (the tab20 table's saturated half, then its light half); a class beyond it takes the last colour
 DEFAULT_PALETTE = (
@@ -41,7 +46,7 @@ class Camera(object):
         self.world_to_view = np.concatenate([rot, -(rot @ eye)[:, None]], 1)
         self.fy = self.fx = 0.5 * self.height / np.tan(np.radians(self.fov_y_deg) / 2.)
         self.cx, self.cy = self.width / 2., self.height / 2.
-        self.params = np.concatenate([self.world_to_view.reshape(-1), [self.fx, self.fy, self.cx, self.cy]])
+        self.params = camera_params(self.world_to_view, self.fx, self.fy, self.cx, self.cy)
 
     @classmethod
     def fit(cls, points, width=1024, height=768, fov_y_deg=60.):
@@ -68,9 +73,34 @@ class Camera(object):
         return np.stack([self.fx * v[:, 0] / v[:, 2] + self.cx, self.fy * v[:, 1] / v[:, 2] + self.cy], 1), v[:, 2]
 
 
+def camera_params(world_to_view, fx, fy, cx, cy):
+    """-> the contiguous (16,) float64 array the rasteriser takes: world_to_view (3,4) in row order, fx, fy, cx, cy"""
+    return np.concatenate([np.asarray(world_to_view, np.float64).reshape(-1), [fx, fy, cx, cy]])
+
+
 def _doubles(a):
     a = np.ascontiguousarray(a, np.float64)
     return a, a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+
+
+def rasterise(verts, faces, params, near, W, H, points=None, point_px=1, scratch=None):
+    """verts (V,3) f32 and faces (F,3) i32, contiguous on the GPU, params: camera_params(), points: None or (tensor, N,
+    stride) -- N scan points of 3 f32, `stride` floats apart -- drawn as squares of point_px pixels, scratch: a
+    RasterScratch of an earlier call with the same V + N, W and H, or None: allocated here
+    -> RasterScratch(q f64 (V+N), sxy i32 (V+N,2), valid u8 (V+N), keys i64 (H,W)): the projection and the depth-tested
+    triangles and points, two launches queued on the current stream.  keys holds the winner of every pixel."""
+    dev = verts.device
+    V, F = int(verts.shape[0]), int(faces.shape[0])
+    pc, N, stride = (verts, 0, 3) if points is None else points
+    if scratch is None:
+        new = lambda dtype, *shape: torch.empty(shape, dtype=dtype, device=dev)
+        scratch = RasterScratch(new(torch.float64, V + N), new(torch.int32, V + N, 2), new(torch.uint8, V + N),
+                                new(torch.int64, max(H, 0), max(W, 0)))   # the library refuses sizes outside 1..8192
+    q, sxy, valid, keys = (t.data_ptr() for t in scratch)
+    cam, cam_p = _doubles(params)
+    _lib.call("rfd_raster_project", dev, V, N, stride, verts.data_ptr(), pc.data_ptr(), cam_p, near, q, sxy, valid)
+    _lib.call("rfd_raster_triangles", dev, V, F, N, W, H, int(point_px), faces.data_ptr(), q, sxy, valid, keys)
+    return scratch
 
 
 def render_scene(scene_mesh, point_cloud, camera, palette=None, point_px=3):
@@ -79,19 +109,16 @@ def render_scene(scene_mesh, point_cloud, camera, palette=None, point_px=3):
     -> RenderResult(image (H,W,3) u8, depth (H,W) f32: z_view, +inf on the background, ids (H,W) i32: -1 background,
     [0, F) a face of scene_mesh, F + n scan point n).  Queued on the current stream; nothing is waited for."""
     verts, faces = scene_mesh.vertices, scene_mesh.faces
+    _lib.need_gpu(verts, *(() if point_cloud is None else (point_cloud,)))
     dev = verts.device
-    if dev.type != 'cuda' or (point_cloud is not None and point_cloud.device.type != 'cuda'):
-        raise RuntimeError("CPU not supported")
-    V, F, K = int(verts.shape[0]), int(faces.shape[0]), int(scene_mesh.obj_class.shape[0])
-    W, H = camera.width, camera.height
-    if point_cloud is None:
-        pc, N, stride = verts, 0, 3
-    else:
+    K, W, H = int(scene_mesh.obj_class.shape[0]), camera.width, camera.height
+    points = None
+    if point_cloud is not None:
         pc = point_cloud[0] if point_cloud.dim() == 3 else point_cloud
         if pc.dtype != torch.float32 or (pc.shape[0] and pc.stride(1) != 1) or (pc.shape[0] > 1 and pc.stride(0) < 3):
             pc = pc.float().contiguous()
         N = int(pc.shape[0])
-        stride = int(pc.stride(0)) if N > 1 else int(pc.shape[1])
+        points = (pc, N, int(pc.stride(0)) if N > 1 else int(pc.shape[1]))
     if palette is None:
         palette = _lib.build_once(_palettes, dev, 'default', lambda: torch.tensor(DEFAULT_PALETTE, dtype=torch.float32,
                                                                                   device=dev), dev)
@@ -99,17 +126,11 @@ def render_scene(scene_mesh, point_cloud, camera, palette=None, point_px=3):
         palette = _lib.as_tensor(palette, dev, torch.float32).reshape(-1, 3).contiguous()
     verts, faces = verts.float().contiguous(), faces.to(torch.int32).contiguous()
     face_obj, obj_class = scene_mesh.face_obj.to(torch.int32).contiguous(), scene_mesh.obj_class.to(torch.int32).contiguous()
+    keys = rasterise(verts, faces, camera.params, camera.near, W, H, points, point_px).keys
     new = lambda dtype, *shape: torch.empty(shape, dtype=dtype, device=dev)
-    q, sxy, valid = new(torch.float64, V + N), new(torch.int32, V + N, 2), new(torch.uint8, V + N)
-    h, w = max(H, 0), max(W, 0)                               # the library refuses sizes outside 1..8192
-    keys = new(torch.int64, h, w)
+    (h, w), F = keys.shape, int(faces.shape[0])
     out = RenderResult(new(torch.uint8, h, w, 3), new(torch.float32, h, w), new(torch.int32, h, w))
-    cam, cam_p = _doubles(camera.params)
     eye, eye_p = _doubles(camera.eye)
-    _lib.call("rfd_raster_project", dev, V, N, stride, verts.data_ptr(), pc.data_ptr(), cam_p, camera.near,
-              q.data_ptr(), sxy.data_ptr(), valid.data_ptr())
-    _lib.call("rfd_raster_triangles", dev, V, F, N, W, H, int(point_px), faces.data_ptr(), q.data_ptr(), sxy.data_ptr(),
-              valid.data_ptr(), keys.data_ptr())
     _lib.call("rfd_raster_shade", dev, F, K, int(palette.shape[0]), W, H, verts.data_ptr(), faces.data_ptr(),
               face_obj.data_ptr(), obj_class.data_ptr(), palette.data_ptr(), eye_p, keys.data_ptr(),
               out.ids.data_ptr(), out.depth.data_ptr(), out.image.data_ptr())

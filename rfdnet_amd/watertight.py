@@ -2,7 +2,8 @@
 (utils/shapenet/1_fuse_shapenetv2.py).  A triangle soup is rendered to depth maps from views on a sphere, the depth maps
 are fused into a truncated signed distance field, and marching cubes on the field gives a closed surface.
 
-The depth maps come from this project's own rasteriser (csrc/raster.hip, the rules of include/rfd_render.h), which is not
+The depth maps come from this project's own rasteriser (csrc/raster.hip, the rules of include/rfd_render.h; its host
+driver and the camera's 16 doubles are render.rasterise and render.camera_params), which is not
 the reference's OpenGL renderer: they are NOT the reference's depth maps pixel for pixel, and neither is the mesh its
 mesh vertex for vertex.  The fusion (csrc/tsdf_fusion.hip, the rules of include/rfd_fuse.h) is the reference's: given the
 same depth maps it returns the reference's field bit for bit (tests/golden/F_FUSE.npz), and marching cubes is PyMCubes'
@@ -16,6 +17,7 @@ import torch
 
 from . import _lib
 from .iscnet.mcubes import marching_cubes_batch
+from .render import camera_params, rasterise
 
 WatertightResult = collections.namedtuple("WatertightResult", "vertices faces tsdf depth")
 
@@ -54,8 +56,7 @@ def fuse_depthmaps(depth, K, R, T, resolution, truncation, voxel_size=None, unkn
     -> tsdf (D,H,W) f32 [, count (D,H,W) i32]: the reference's pyfusion.tsdf_gpu.  unobserved: the value of a voxel that no
     view gave a valid sample: '-truncation' (tsdf_gpu's), '+truncation' (the field after the reference's tsdfmask_gpu
     pass: `tsdf[mask == 0] = truncation`) or a number.  view_chunk: include/rfd_fuse.h (0: the library's choice)."""
-    if not torch.is_tensor(depth) or depth.device.type != 'cuda':
-        raise RuntimeError("CPU not supported")
+    _lib.need_gpu(depth)
     dev = depth.device
     D, H, W = (int(resolution),) * 3 if np.ndim(resolution) == 0 else (int(s) for s in resolution)
     if depth.dim() != 3:
@@ -81,28 +82,22 @@ def fuse_depthmaps(depth, K, R, T, resolution, truncation, voxel_size=None, unkn
 @torch.no_grad()
 def render_depthmaps(vertices, faces, rotations, image_size, focal, znf, offset):
     """vertices (V,3) f32 and faces (F,3) i32 on the GPU, in the frame the views look at (the reference's normalised cube),
-    rotations (n,3,3) float64 on the host -> (n,image_size,image_size) f32: per view the existing rasteriser (projection and
-    depth-tested triangles, no scan points), then rfd_depth_from_keys into the view's slot of the stack.
+    rotations (n,3,3) float64 on the host -> (n,image_size,image_size) f32: per view render.rasterise (projection and
+    depth-tested triangles, no scan points) on the first view's scratch, then rfd_depth_from_keys into the view's slot
+    of the stack.
 
     The camera's world-to-view is [R | (0,0,1)] and its principal point (c + 0.5, c + 0.5) with c = image_size / 2: the
     rasteriser's pixel (i, j) has its centre at (i + 0.5, j + 0.5), the fusion looks a projected voxel up at the pixel whose
     INTEGER coordinates are nearest to (u, v) under a principal point of (c, c); the half pixel makes the two agree."""
-    dev = vertices.device
-    nv, nf, S = int(vertices.shape[0]), int(faces.shape[0]), int(image_size)
-    n = len(rotations)
-    new = lambda dtype, *shape: torch.empty(shape, dtype=dtype, device=dev)
-    q, sxy, valid = new(torch.float64, nv), new(torch.int32, nv, 2), new(torch.uint8, nv)
-    keys, stack = new(torch.int64, max(S, 0), max(S, 0)), new(torch.float32, n, max(S, 0), max(S, 0))
-    cam = np.empty(16, np.float64)
-    cam[12:] = focal, focal, S / 2. + 0.5, S / 2. + 0.5
-    cam_p = cam.ctypes.data_as(_lib.C.POINTER(_lib.C.c_double))
+    dev, S, n = vertices.device, int(image_size), len(rotations)
+    stack = torch.empty(n, max(S, 0), max(S, 0), dtype=torch.float32, device=dev)
+    scratch = None
     for v in range(n):
-        cam[:12] = np.concatenate([np.asarray(rotations[v], np.float64), [[0.], [0.], [1.]]], 1).reshape(-1)
-        _lib.call("rfd_raster_project", dev, nv, 0, 3, vertices.data_ptr(), vertices.data_ptr(), cam_p, float(znf[0]),
-                  q.data_ptr(), sxy.data_ptr(), valid.data_ptr())
-        _lib.call("rfd_raster_triangles", dev, nv, nf, 0, S, S, 1, faces.data_ptr(), q.data_ptr(), sxy.data_ptr(),
-                  valid.data_ptr(), keys.data_ptr())
-        _lib.call("rfd_depth_from_keys", dev, S, S, keys.data_ptr(), float(znf[1]), float(offset), stack[v].data_ptr())
+        cam = camera_params(np.concatenate([np.asarray(rotations[v], np.float64), [[0.], [0.], [1.]]], 1),
+                            focal, focal, S / 2. + 0.5, S / 2. + 0.5)
+        scratch = rasterise(vertices, faces, cam, float(znf[0]), S, S, scratch=scratch)
+        _lib.call("rfd_depth_from_keys", dev, S, S, scratch.keys.data_ptr(), float(znf[1]), float(offset),
+                  stack[v].data_ptr())
     return stack
 
 
@@ -129,9 +124,7 @@ def watertight(vertices, faces, resolution=256, n_views=200, image_size=640, foc
     The depth maps are this rasteriser's, not OpenGL's: the result is not the reference's mesh vertex for vertex (module
     docstring).  The truncated field has a second zero crossing one truncation behind every surface that is seen from one
     side only, so a closed thick shape gets an inner shell, as it does in the reference."""
-    if not (torch.is_tensor(vertices) and torch.is_tensor(faces)) or vertices.device.type != 'cuda' or \
-            faces.device.type != 'cuda':
-        raise RuntimeError("CPU not supported")
+    _lib.need_gpu(vertices, faces)
     resolution = int(resolution)
     voxel = 1. / resolution
     v64 = vertices.double().reshape(-1, 3)

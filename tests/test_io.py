@@ -2,6 +2,7 @@
 import os
 
 import numpy as np
+import pytest
 
 from rfdnet_amd import io
 
@@ -88,3 +89,24 @@ def test_save_visualization_files(tmp_path):
                                             'proposal_1_mesh.ply', 'proposal_4_mesh.ply']
     d = np.load(tmp_path / '000000_pred_confident_nms_bbox.npz')
     assert d['obbs'].shape == (2, 7) and d['proposal_map'].shape == (2, 1) and d['proposal_map'].dtype == np.int64
+
+
+def test_read_mesh_reads_off_obj_and_ply(tmp_path):
+    rng = np.random.default_rng(1)
+    v = rng.uniform(-1, 1, (7, 3)).astype(np.float32).astype(np.float64)       # exact in the .ply's float32
+    with open(tmp_path / "a.off", "w") as fh:                                  # a quad and a triangle, colour columns
+        fh.write("COFF\n7 2 0\n")
+        for r in v:
+            fh.write("%.17g %.17g %.17g 255 0 0 255\n" % tuple(r))
+        fh.write("4 0 1 2 3\n3 4 5 6\n")
+    want = np.array([[0, 1, 2], [0, 2, 3], [4, 5, 6]], np.int32)
+    with open(tmp_path / "a.obj", "w") as fh:
+        fh.write("".join("v %.17g %.17g %.17g\n" % tuple(r) for r in v) + "f 1 2 3 4\nf 5 6 7\n")
+    io.write_mesh_ply(str(tmp_path / "a.ply"), v, want)
+    for ext in (".off", ".obj", ".ply"):
+        gv, gf = io.read_mesh(str(tmp_path / ("a" + ext)))
+        assert gv.dtype == np.float64 and gf.dtype == np.int32, ext
+        assert gv.shape == (7, 3) and np.array_equal(gv, v), ext
+        assert np.array_equal(gf, want), ext
+    with pytest.raises(ValueError, match=r"x\.stl.*\.off.*\.obj.*\.ply"):
+        io.read_mesh(str(tmp_path / "x.stl"))

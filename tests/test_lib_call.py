@@ -142,3 +142,15 @@ def test_a_library_without_a_stamp_is_stale(tmp_path, monkeypatch):
     with open(build.STAMP_PATH, "w") as f:
         f.write(build._stamp())
     assert not build.is_stale() and os.path.exists(build.LIB_PATH)
+
+
+# ------------------------------------------------------------------------------------------------------ the guard ----
+def test_need_gpu_refuses_whatever_is_no_device_tensor():
+    import numpy as np
+    _lib.need_gpu()
+    for bad in (torch.zeros(2), np.zeros(2), None):
+        with pytest.raises(RuntimeError, match="CPU not supported"):
+            _lib.need_gpu(bad)
+    meta = types.SimpleNamespace(device=types.SimpleNamespace(type='cuda'))    # looks like one, is no tensor
+    with pytest.raises(RuntimeError, match="CPU not supported"):
+        _lib.need_gpu(meta)

@@ -172,3 +172,19 @@ def test_is_watertight_on_host_tensors():
         assert ms.is_watertight(torch.from_numpy(cases.normalised(name)[1]))
     f = torch.from_numpy(cases.cube()[1])
     assert not ms.is_watertight(f[1:]) and not ms.is_watertight(torch.cat([f, f[:1]])) and not ms.is_watertight(f[:0])
+
+
+def test_unit_cube_gives_the_bits_of_the_numpy_lines_it_replaces(tmp_path):
+    from rfdnet_amd import mesh_sample as ms
+    v = cases.cube()[0] * 3.7 + np.array([0.3, -1.7, 2.1])
+    lo, hi = v.min(0), v.max(0)
+    loc, scale = (lo + hi) / 2, float((hi - lo).max())
+    want = (v - loc) * (1 / scale)
+    got, got_loc, got_scale = ms.unit_cube(torch.from_numpy(v))
+    assert got.dtype == torch.float64 and got_loc.dtype == torch.float64 and type(got_scale) is float
+    assert got.numpy().tobytes() == want.tobytes()
+    assert got_loc.numpy().tobytes() == loc.tobytes() and got_scale == scale
+    from rfdnet_amd import io                                                   # and so the .off the tool writes
+    io.write_off(str(tmp_path / "got.off"), got.numpy(), cases.cube()[1])
+    io.write_off(str(tmp_path / "want.off"), want, cases.cube()[1])
+    assert (tmp_path / "got.off").read_bytes() == (tmp_path / "want.off").read_bytes()

@@ -179,3 +179,18 @@ def test_camera_fit_keeps_the_scans_box_in_the_image(w, h):
     assert top[0, 1] < h / 2.                                                      # +z of the scan is up in the picture
     same = render.Camera.fit(torch.from_numpy(scan)[None], width=w, height=h)
     np.testing.assert_array_equal(same.params, cam.params)
+
+
+def test_camera_params_is_the_array_the_rasteriser_takes():
+    from rfdnet_amd.watertight import views_on_sphere
+    cam = render.Camera.fit(cases.ragged_scan(), width=96, height=64)
+    got = render.camera_params(cam.world_to_view, cam.fx, cam.fy, cam.cx, cam.cy)
+    assert got.dtype == np.float64 and got.shape == (16,) and got.flags['C_CONTIGUOUS']
+    np.testing.assert_array_equal(got, cam.params)
+    # render_depthmaps' convention: [R | (0,0,1)], fx = fy = focal, the principal point at S / 2 + 0.5
+    R = views_on_sphere(3)[1]
+    want = np.array([R[0, 0], R[0, 1], R[0, 2], 0., R[1, 0], R[1, 1], R[1, 2], 0., R[2, 0], R[2, 1], R[2, 2], 1.,
+                     48., 48., 24.5, 24.5])
+    got = render.camera_params(np.concatenate([R, [[0.], [0.], [1.]]], 1), 48, 48, 48 / 2. + 0.5, 48 / 2. + 0.5)
+    assert got.dtype == np.float64 and got.flags['C_CONTIGUOUS']
+    np.testing.assert_array_equal(got, want)

@@ -12,15 +12,11 @@ numbers.  Seeded weights (synthetic.load_seeded): the cost does not depend on th
 import argparse
 import json
 import os
-import statistics
-import sys
 
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if ROOT not in sys.path:
-    sys.path.insert(0, ROOT)
+from cost_common import ROOT, device_ms
 
 TORCH_OPS_OF_THE_MODULE = 8 + 3 + 3 + 2 * 2 + 3
 
@@ -36,21 +32,6 @@ def torch_encoder(enc, p, x, c):
         net = lin(torch.relu(torch.cat([net, pooled], dim=2)), fc.weight, fc.bias)
     net = net.max(dim=1)[0]
     return lin(net, enc.fc_mean.weight, enc.fc_mean.bias), lin(net, enc.fc_logstd.weight, enc.fc_logstd.bias)
-
-
-def device_ms(fn, reps, windows=5):
-    fn()
-    torch.cuda.synchronize()
-    out = []
-    for _ in range(windows):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(reps):
-            fn()
-        b.record()
-        b.synchronize()
-        out.append(a.elapsed_time(b) / reps)
-    return statistics.median(out), min(out), max(out)
 
 
 def main():

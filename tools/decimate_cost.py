@@ -10,20 +10,11 @@ refinement step (Generator3D.refine_meshes with weights drawn on the device, see
 two-step call minus that of a one-step call, so the once-per-call set-up cancels) on the full and on the decimated
 meshes.  Beside them the marching-cubes extraction of the same scene, timed the same way."""
 import argparse
-import json
-import os
-import sys
 
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if ROOT not in sys.path:
-    sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-
-import render_cost  # noqa: E402
-from render_cost import timed  # noqa: E402
+from cost_common import GRID, emit, need_gpu_or_exit, object_grids, placement_draws, timed
 
 PADDING = 0.1
 
@@ -42,10 +33,10 @@ def measure(label, n_obj, onet, reps, warmup):
     from rfdnet_amd.iscnet.decimate import decimate_meshes
     from rfdnet_amd.iscnet.mcubes import marching_cubes_batch
     rng = np.random.default_rng(5)
-    render_cost.placement_draws(rng, n_obj)                      # the same stream, so the same objects, as render_cost
-    grids = render_cost.object_grids(rng, n_obj)
+    placement_draws(rng, n_obj)                      # the same stream, so the same objects, as render_cost
+    grids = object_grids(rng, n_obj)
     box = 1 + PADDING
-    a = box / (render_cost.GRID - 1)
+    a = box / (GRID - 1)
     extract = lambda: marching_cubes_batch(grids, 0., return_flat=True, affine=(a, -1.5 * a - 0.5 * box))
     full = extract()
     gen, dec = onet.generator, onet.decoder
@@ -53,7 +44,7 @@ def measure(label, n_obj, onet, reps, warmup):
     with torch.no_grad():
         fold = dec.fold(torch.zeros(n_obj, onet.z_dim, device="cuda"),
                         torch.from_numpy(code_rng.normal(0, 1, (n_obj, 512)).astype(np.float32)).cuda())
-    row = {"scene": label, "objects": n_obj, "grid": render_cost.GRID, "vertices": int(full[2][-1]),
+    row = {"scene": label, "objects": n_obj, "grid": GRID, "vertices": int(full[2][-1]),
            "faces": int(full[3][-1]), "marching_cubes": timed(extract, reps, warmup),
            "refine_step_full": refine_step_ms(gen, full, fold, reps, warmup), "cells": {}}
     for cells in (16, 32):
@@ -73,8 +64,7 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("decimate_cost measures on a GPU: none is visible")
+    need_gpu_or_exit("decimate_cost")
     from rfdnet_amd import synthetic
     from rfdnet_amd.iscnet.config import Config
     from rfdnet_amd.iscnet.occupancy_net import ONet
@@ -86,11 +76,7 @@ def main():
             measure("headline", 256, onet, args.reps, args.warmup)]
     result = {"tool": "decimate_cost", "device": torch.cuda.get_device_name(0), "reps": args.reps, "warmup": args.warmup,
               "rows": rows}
-    text = json.dumps(result)
-    print(text)
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write(text + "\n")
+    emit(result, args.out)
 
 
 if __name__ == "__main__":

@@ -13,32 +13,19 @@ the pairs evaluated per step (from the shapes), the calls through the C ABI and 
 under torch's sync debug mode).  For the device method also the loop alone (run_fit), the kernel launches (two per step),
 and both points-per-thread instantiations of fit_nn_kernel: the one fit.PPT_SWITCH chooses and the other."""
 import argparse
-import json
 import os
 import statistics
-import sys
 import warnings
 
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if ROOT not in sys.path:
-    sys.path.insert(0, ROOT)
+from cost_common import ROOT, emit, event_ms
 
 
 class Mesh(object):
     def __init__(self, vertices):
         self.vertices = vertices
-
-
-def event_ms(fn):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b)
 
 
 def host_syncs(fn):
@@ -150,12 +137,9 @@ def main():
     rows = [measure("F_FIT", f_fit_case(), args.reps), measure("demo-sized, 13 objects", demo_case(args.points), args.reps)]
     line = {"tool": "fit_cost", "device": torch.cuda.get_device_name(0), "rounds": args.reps, "ppt_switch": fit.PPT_SWITCH,
             "rows": rows}
-    text = json.dumps(line)
-    print(text)
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as fh:
-            fh.write(text + "\n")
+    emit(line, args.out)
 
 
 if __name__ == "__main__":

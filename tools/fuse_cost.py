@@ -16,28 +16,13 @@ tools/render_cost.py's dented marching-cubes spheres (48^3, about 18 600 faces),
 The bytes the gather moves need a counter run of its own (rocprofv3 --pmc, nothing else traced); this tool does not
 make one and says so."""
 import argparse
-import json
-import os
-import sys
 
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if ROOT not in sys.path:
-    sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-
-from render_cost import timed  # noqa: E402
+from cost_common import emit, need_gpu_or_exit, real_mesh, timed
 
 STRATEGIES = (0, 1, 2, 4, 8, 25, 50)          # view_chunk: 0 = all views in one launch
-
-
-def real_mesh():
-    import render_cost
-    from rfdnet_amd.iscnet.mcubes import marching_cubes_batch
-    v, f = marching_cubes_batch(render_cost.object_grids(np.random.default_rng(5), 1), 0.)[0]
-    return v, f
 
 
 def torch_fuse(depth, K, R, T, res, vx_size, truncation, unobserved):
@@ -78,8 +63,7 @@ def main():
     ap.add_argument("--views", type=int, default=200)
     ap.add_argument("--image_size", type=int, default=640)
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("fuse_cost measures on a GPU: none is visible")
+    need_gpu_or_exit("fuse_cost")
     from rfdnet_amd import watertight as wt
     from rfdnet_amd.iscnet.mcubes import marching_cubes_batch
     res, V, S = args.resolution, args.views, args.image_size
@@ -156,11 +140,7 @@ def main():
                        "watertight_vertices": int(state["mesh"][0].shape[0]), "watertight_faces": int(state["mesh"][1].shape[0])},
               "fuse": rows, "fuse_second_pass": second_pass, "torch_ops": yard, "stages": stages, "watertight_call": whole,
               "gather_bytes": "not measured: needs a counter run of its own"}
-    text = json.dumps(result)
-    print(text)
-    if args.out:
-        with open(args.out, "w") as fh:
-            fh.write(text + "\n")
+    emit(result, args.out)
 
 
 if __name__ == "__main__":

@@ -12,17 +12,11 @@ includes its one device-to-host copy, as the torch figure includes the reference
 import argparse
 import json
 import os
-import sys
 
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "tools")):
-    if p not in sys.path:
-        sys.path.insert(0, p)
-
-from completion_cost import device_ms  # noqa: E402
+from cost_common import ROOT, device_ms
 
 
 def nearest(a, b, l1=False):

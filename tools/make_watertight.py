@@ -12,27 +12,11 @@ import json
 import os
 import sys
 
-import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
-
-
-def read_mesh(path):
-    from rfdnet_amd import io
-    ext = os.path.splitext(path)[1].lower()
-    if ext == ".off":
-        v, faces = io.read_off(path)
-        tris = [[f[0], f[k], f[k + 1]] for f in faces for k in range(1, len(f) - 1)]      # polygons as fans
-        return v[:, :3], np.asarray(tris, np.int32).reshape(-1, 3)
-    if ext == ".obj":
-        return io.read_obj(path)
-    if ext == ".ply":
-        v, f = io.read_mesh_ply(path)
-        return v.astype(np.float64), f.astype(np.int32)
-    raise SystemExit("make_watertight reads .off, .obj and .ply, not %s" % path)
 
 
 def main():
@@ -48,7 +32,9 @@ def main():
         raise SystemExit("make_watertight runs on a GPU: none is visible")
     from rfdnet_amd import io
     from rfdnet_amd.watertight import watertight
-    v, f = read_mesh(args.input)
+    if os.path.splitext(args.input)[1].lower() not in (".off", ".obj", ".ply"):
+        raise SystemExit("make_watertight reads .off, .obj and .ply, not %s" % args.input)
+    v, f = io.read_mesh(args.input)
     if not len(v) or not len(f):
         raise SystemExit("%s holds no triangles" % args.input)
     dev = torch.device("cuda")

@@ -11,50 +11,12 @@ the scene's own reconstruction time from the benchmark records profiles/r06_benc
 import argparse
 import json
 import os
-import statistics
-import sys
 import types
 
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if ROOT not in sys.path:
-    sys.path.insert(0, ROOT)
-
-GRID = 48
-
-
-def event_ms(fn):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b)
-
-
-def timed(fn, reps, warmup):
-    for _ in range(warmup):
-        fn()
-    ms = [event_ms(fn) for _ in range(reps)]
-    return {"ms": statistics.median(ms), "ms_min": min(ms), "ms_max": max(ms)}
-
-
-def placement_draws(rng, n_obj):
-    """the two draws that place a box used again (centre offsets, heading noise); the objects' dents are drawn after them"""
-    return rng.uniform(-1.5, 1.5, (n_obj, 3)), rng.normal(0, 0.3, n_obj)
-
-
-def object_grids(rng, n_obj):
-    """(n_obj, GRID, GRID, GRID) f32 value grids on the GPU: a sphere with a few dents of its own per object"""
-    g = np.stack(np.meshgrid(*[np.arange(GRID, dtype=np.float32)] * 3, indexing='ij'), -1) - (GRID - 1) / 2.
-    r = np.linalg.norm(g, axis=-1)
-    grids = torch.empty(n_obj, GRID, GRID, GRID, device="cuda")
-    for k in range(n_obj):
-        w = rng.normal(0, 1, 3)
-        grids[k] = torch.from_numpy((0.45 * GRID - r + 1.5 * np.sin(g @ w / 4.)).astype(np.float32))
-    return grids
+from cost_common import ROOT, emit, need_gpu_or_exit, object_grids, placement_draws, timed
 
 
 def scene_inputs(n_obj, points=80000):
@@ -102,17 +64,12 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("render_cost measures on a GPU: none is visible")
+    need_gpu_or_exit("render_cost")
     rows = [measure("demo-sized", 13, "r06_bench_demo.json", args.reps, args.warmup),
             measure("headline", 256, "r06_bench_headline.json", args.reps, args.warmup)]
     result = {"tool": "render_cost", "device": torch.cuda.get_device_name(0), "reps": args.reps, "warmup": args.warmup,
               "rows": rows}
-    text = json.dumps(result)
-    print(text)
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write(text + "\n")
+    emit(result, args.out)
 
 
 if __name__ == "__main__":

@@ -2,9 +2,10 @@
 
     python tools/sample_cost.py [--out profiles/sample_cost.json] [--reps 20] [--warmup 3] [--points 100000]
 
-Two meshes, both moved into the unit cube as tools/sample_mesh.py --resize does: tools/fuse_cost.py's dented
-marching-cubes sphere (48^3, about 18 700 faces), and watertight() of it at 256^3 (about 900 000 faces).  Per mesh,
-device milliseconds between HIP events (the median, minimum and maximum of `reps` calls after `warmup`):
+Two meshes, both moved into the unit cube as tools/sample_mesh.py --resize does (mesh_sample.unit_cube):
+tools/cost_common.py's dented marching-cubes sphere (48^3, about 18 700 faces), and watertight() of it at 256^3 (about
+900 000 faces).  Per mesh, device milliseconds between HIP events (the median, minimum and maximum of `reps` calls after
+`warmup`):
 
   build             MeshIntersector(vertices, faces, 512): the mesh check, the rescale, the cell lists (two read-backs)
   pairs             (cell, triangle) pairs in the lists
@@ -15,26 +16,10 @@ device milliseconds between HIP events (the median, minimum and maximum of `reps
 On the smaller mesh, `torch_ops` is the same containment (rules C2 - C6 of include/rfd_sample.h over ALL triangles) written
 as dense float64 torch operations in chunks of points on the same device; the tool asserts that it gives the same booleans."""
 import argparse
-import json
-import os
-import sys
 
-import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if ROOT not in sys.path:
-    sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-
-from render_cost import timed  # noqa: E402
-from fuse_cost import real_mesh  # noqa: E402
-
-
-def unit(v):
-    v = v.double()
-    lo, hi = v.amin(0), v.amax(0)
-    return ((v - (lo + hi) / 2) * (1 / (hi - lo).max())).contiguous()
+from cost_common import emit, need_gpu_or_exit, real_mesh, timed
 
 
 def torch_contains(mi, points, chunk=2048):
@@ -110,20 +95,17 @@ def main():
     ap.add_argument("--points", type=int, default=100000)
     ap.add_argument("--resolution", type=int, default=256, help="of the watertight() that makes the larger mesh")
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("sample_cost measures on a GPU: none is visible")
+    need_gpu_or_exit("sample_cost")
+    from rfdnet_amd.mesh_sample import unit_cube
     from rfdnet_amd.watertight import watertight
+    unit = lambda v: unit_cube(v.double())[0].contiguous()
     v, f = real_mesh()
     rows = [measure("dented sphere 48^3", unit(v), f.to(torch.int32).contiguous(), args, True)]
     wv, wf = watertight(v, f, resolution=args.resolution)
     rows.append(measure("watertight() of it at %d^3" % args.resolution, unit(wv), wf.contiguous(), args, False))
     result = {"tool": "sample_cost", "device": torch.cuda.get_device_name(0), "reps": args.reps, "warmup": args.warmup,
               "hash_resolution": 512, "meshes": rows}
-    text = json.dumps(result)
-    print(text)
-    if args.out:
-        with open(args.out, "w") as fh:
-            fh.write(text + "\n")
+    emit(result, args.out)
 
 
 if __name__ == "__main__":

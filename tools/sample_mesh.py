@@ -21,7 +21,6 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 
 def main():
@@ -43,16 +42,14 @@ def main():
         raise SystemExit("sample_mesh reads .off and .obj, not %s" % args.input)
     if not torch.cuda.is_available():
         raise SystemExit("sample_mesh runs on a GPU: none is visible")
-    from make_watertight import read_mesh
     from rfdnet_amd import io, mesh_sample
-    v, f = read_mesh(args.input)
+    v, f = io.read_mesh(args.input)
     if not len(v) or not len(f):
         raise SystemExit("%s holds no triangles" % args.input)
     loc, scale = np.zeros(3), 1.
     if args.resize:
-        lo, hi = v.min(0), v.max(0)
-        loc, scale = (lo + hi) / 2, float((hi - lo).max())
-        v = (v - loc) * (1 / scale)
+        v, loc, scale = mesh_sample.unit_cube(torch.from_numpy(v))
+        v, loc = v.numpy(), loc.numpy()
     dev = torch.device("cuda")
     vt, ft = torch.from_numpy(np.ascontiguousarray(v, np.float64)).to(dev), torch.from_numpy(f).to(dev)
     gen = torch.Generator(device=dev).manual_seed(args.seed)
