@@ -8,6 +8,7 @@ write the reference's output files.
   python demo.py --synthetic 10 --out out/synth --with_normals     (PLYs with per-vertex nx ny nz)
   python demo.py --synthetic 10 --out out/synth --refinement_step 30   (meshes refined against the occupancy field)
   python demo.py --synthetic 10 --out out/synth --decimate_cells 16    (meshes thinned by vertex clustering, 16^3 cells)
+  python demo.py --synthetic 10 --out out/synth --simplify_nfaces 500   (meshes collapsed to 500 faces each, watertight)
   python demo.py --synthetic 10 --out out/synth --render --post_processing  (scene_objects.ply and pred.png as well)
 
 Weights: --weight <pretrained_weight.pth> (reference checkpoint, key names kept);
@@ -58,6 +59,10 @@ def build_parser():
     ap.add_argument("--decimate_cells", type=int, default=None,
                     help="thin every mesh by vertex clustering on an N^3 grid over its cube before normals and "
                          "refinement (Generator3D.set_decimation; generation.decimate_cells, 0 = off)")
+    ap.add_argument("--simplify_nfaces", type=int, default=None,
+                    help="simplify every mesh to at most N faces by quadric edge collapse on the device, after "
+                         "--decimate_cells and before normals and refinement (Generator3D.set_simplification; "
+                         "generation.simplify_faces, 0 = off)")
     ap.add_argument("--render", action="store_true",
                     help="place every mesh in its box (iscnet.scene.place_objects), render scan and meshes on the device "
                          "and write scene_objects.ply and pred.png beside the other files (demo.py:329-377; needs "
@@ -77,7 +82,8 @@ def main():
     from rfdnet_amd.iscnet.network import ISCNet
 
     gen = {k: v for k, v in (('resolution_0', args.resolution_0), ('upsampling_steps', args.upsampling_steps),
-                             ('refinement_step', args.refinement_step), ('decimate_cells', args.decimate_cells))
+                             ('refinement_step', args.refinement_step), ('decimate_cells', args.decimate_cells),
+                             ('simplify_faces', args.simplify_nfaces))
            if v is not None}
     if args.with_normals:
         gen['with_normals'] = True

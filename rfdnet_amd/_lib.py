@@ -18,7 +18,7 @@ _sz = C.c_size_t
 _d = C.c_double
 
 # name -> (restype, argtypes[, OPTIONAL]): exactly the prototypes of include/rfd_pointnet2.h / rfd_occ.h /
-# rfd_chamfer.h / rfd_eval.h / rfd_latent.h / rfd_loss.h / rfd_fit.h / rfd_render.h / rfd_decimate.h / rfd_fuse.h / rfd_sample.h.  OPTIONAL marks the test hooks, which a deployment build (RFD_NO_TEST_HOOKS=1, build.py)
+# rfd_chamfer.h / rfd_eval.h / rfd_latent.h / rfd_loss.h / rfd_fit.h / rfd_render.h / rfd_decimate.h / rfd_simplify.h / rfd_fuse.h / rfd_sample.h.  OPTIONAL marks the test hooks, which a deployment build (RFD_NO_TEST_HOOKS=1, build.py)
 # leaves out.
 OPTIONAL = "optional"
 ABI = {
@@ -107,7 +107,15 @@ ABI = {
     "rfd_decimate_parity": (_i, [_i, _i, _i, _f, _f, _f, _f, _f, _f, _f]),
     "rfd_decimate_cell_solve": (_i, [_i, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _f, _f, _f, C.c_double, _f, _f]),
     "rfd_decimate_compact_faces": (_i, [_i, _i, _f, _f, _f, _f, _f, _f, _f, _f]),
-    "rfd_depth_from_keys": (_i, [_i, _i, _f, _fl, _fl, _f, _f]),
+    "rfd_simplify_init": (_i, [_i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _f, _f, _f]),
+    "rfd_simplify_quadrics": (_i, [_i, _i, _f, _f, _f, _f, _f, _f]),
+    "rfd_simplify_edges": (_i, [_i, _i, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f]),
+    "rfd_simplify_edge_costs": (_i, [_i, _i, _i, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f]),
+    "rfd_simplify_vertex_min": (_i, [_i, _i, _i, _f, _f, _f, _f, _f, _f, _f]),
+    "rfd_simplify_select": (_i, [_i, _i, _f, _f, _f, _f, _f, _f, _f]),
+    "rfd_simplify_apply": (_i, [_i, _i, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f]),
+    "rfd_simplify_compact_faces": (_i, [_i, _i, _i, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f]),
+    "rfd_depth_from_keys":(_i, [_i, _i, _f, _fl, _fl, _f, _f]),
     "rfd_tsdf_fuse": (_i, [_i, _i, _i, _f, _f, _f, _f, _i, _i, _i, _fl, _fl, _i, _fl, _i, _f, _f, _f]),
     "rfd_sample_rescale": (_i, [_i, _f, _d, _d, _d, _d, _d, _d, _i, _f, _f, _f]),
     "rfd_sample_cells": (_i, [_i, _f, _i, _f, _f, _f]),

@@ -2,8 +2,8 @@
 a scene at once on the flat buffers marching cubes leaves (csrc/mesh_decimate.hip, include/rfd_decimate.h: the five
 rules; tests/decimate_f64.py restates them in numpy float64).
 
-The reference thins a mesh by sequential quadric edge collapse on the host (generator.py:189-191, simplify_mesh);
-that algorithm stays out.  Clustering fits the machine instead: every vertex falls into a cell
+The reference thins a mesh by sequential quadric edge collapse on the host (generator.py:189-191, simplify_mesh); its
+parallel form, with a face budget and the topology kept, is simplify.py.  Clustering is the cheap thinning: every vertex falls into a cell
 of a `cells`^3 grid over its mesh's cube, every occupied cell becomes one vertex placed where the quadrics of the
 faces around it are smallest (kept inside the cell), faces that collapse are dropped, coincident survivors are
 reduced mod 2 (so a closed mesh keeps even edge counts), and what no face names any more is compacted away.

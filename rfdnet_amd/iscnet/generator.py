@@ -65,8 +65,9 @@ class Generator3D(object):
                  sample=False, use_cls_for_completion=False, simplify_nfaces=None,
                  preprocessor=None):
         if refinement_step or simplify_nfaces is not None:
-            # disabled by ISCNet_test.yaml:64-66; libsimplify is out of scope, refinement is switched on
-            # by set_refinement() (ONet does, from generation.refinement_step)
+            # disabled by ISCNet_test.yaml:64-66; both are switched on by setters: simplification by set_simplification()
+            # (edge collapse on the device, not libsimplify's collapse order), refinement by set_refinement() (ONet does,
+            # from generation.refinement_step)
             raise NotImplementedError("simplification is not implemented; refinement is enabled with "
                                       "Generator3D.set_refinement(steps), not by the constructor")
         self.model = model
@@ -89,6 +90,7 @@ class Generator3D(object):
         self.last_normals = None        # with_normals: the (V,3) f32 normals of the last extract_meshes(), all meshes
         self.refine_eps_source, self.refine_seed = 'numpy', None       # set_refinement()
         self.decimate_cells = 0         # set_decimation()
+        self.simplify_faces = 0         # set_simplification()
         self._round0_cache = _lib.ArtefactCache(64)     # made here: the worker views of one network share it
 
     def set_refinement(self, steps, eps_source='numpy', seed=None):
@@ -110,12 +112,24 @@ class Generator3D(object):
     def set_decimation(self, cells):
         """Thin every extracted mesh by vertex clustering on a `cells`^3 grid over the generator's cube (decimate.py), between
         marching cubes and the normals / the refinement: where the reference calls simplify_mesh (generator.py:189-191).
-        0 or None = off (the default).  Not the reference's algorithm: its sequential edge collapse stays unsupported
-        (simplify_nfaces raises)."""
+        0 or None = off (the default).  Not the reference's algorithm: edge collapse to a face budget is set_simplification()
+        (the constructor's simplify_nfaces raises)."""
         cells = int(cells or 0)
         if cells < 0:
             raise ValueError("decimation cells must be >= 0")
         self.decimate_cells = cells
+        return self
+
+    def set_simplification(self, n_faces):
+        """Simplify every extracted mesh to at most `n_faces` faces by quadric edge collapse on the device (simplify.py),
+        where the reference calls simplify_mesh (generator.py:189-191): before the normals and the refinement, and after
+        set_decimation()'s clustering when both are set (cluster coarsely, then collapse to the budget).  0 or None = off
+        (the default).  The reference's result class, not its collapse order; the constructor's
+        simplify_nfaces still raises."""
+        n_faces = int(n_faces or 0)
+        if n_faces < 0:
+            raise ValueError("simplification target must be >= 0 faces")
+        self.simplify_faces = n_faces
         return self
 
     def _needs_fold(self):
@@ -274,8 +288,8 @@ class Generator3D(object):
         """fold = (table, fc_p_w) of the codes the grids came from: vertex normals from the decoder's gradient
         (Generator3D.estimate_normals), one launch for all meshes; with set_refinement(), the refinement of all meshes
         (refine_meshes) -- after the normals, which belong to the unrefined vertices as in the reference (generator.py:173-195).
-        With set_decimation() the meshes are thinned first: normals, refinement, last_buffers and the Mesh list are those of
-        the decimated meshes."""
+        With set_decimation() / set_simplification() the meshes are thinned first: normals, refinement, last_buffers and the
+        Mesh list are those of the thinned meshes."""
         from .mcubes import marching_cubes_batch
         thr = self.logit_threshold()
         n = grids.shape[1]
@@ -294,6 +308,9 @@ class Generator3D(object):
             K = len(vend) - 1
             v, f, vend, tend = decimate_meshes(v, f, vend, tend, self.decimate_cells, lo=np.full((K, 3), -box_size / 2),
                                                h=np.full(K, box_size / self.decimate_cells))
+        if self.simplify_faces:
+            from .simplify import simplify_meshes
+            v, f, vend, tend, _ = simplify_meshes(v, f, vend, tend, self.simplify_faces)
         self.last_normals = None
         refine = self.refinement_step > 0
         if refine and fold is None:
@@ -301,7 +318,7 @@ class Generator3D(object):
         nrm = None
         if fold is not None and (self.with_normals or not refine):
             # generator.py:173-176: normals of every non-empty mesh; the reference leaves them None on an empty one
-            # (decimated vertices are f32; the normals kernel reads f64: widened, exact)
+            # (decimated vertices are f32, simplified ones f64; the normals kernel reads f64: widened, exact)
             nrm = self.last_normals = self.model.decoder.normals(v if v.dtype == torch.float64 else v.double(), vend,
                                                                  fold[0], fold[1])
         if refine:

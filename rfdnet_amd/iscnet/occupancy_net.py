@@ -44,6 +44,8 @@ class ONet(nn.Module):
                 self.generator.set_refinement(gen['refinement_step'])
             if gen.get('decimate_cells'):       # not a key of the reference's config files: absent = off
                 self.generator.set_decimation(gen['decimate_cells'])
+            if gen.get('simplify_faces'):       # nor is this one (the reference's simplify_nfaces still raises)
+                self.generator.set_simplification(gen['simplify_faces'])
 
     def enable_latent_encoder(self):
         """Attach the latent encoder (z_dim > 0; occupancy_net.py:40-43) in front of the decoder, so that state_dict()
