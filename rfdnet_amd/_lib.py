@@ -18,7 +18,7 @@ _sz = C.c_size_t
 _d = C.c_double
 
 # name -> (restype, argtypes[, OPTIONAL]): exactly the prototypes of include/rfd_pointnet2.h / rfd_occ.h /
-# rfd_chamfer.h / rfd_eval.h / rfd_latent.h / rfd_loss.h / rfd_fit.h / rfd_render.h / rfd_decimate.h / rfd_simplify.h / rfd_fuse.h / rfd_sample.h.  OPTIONAL marks the test hooks, which a deployment build (RFD_NO_TEST_HOOKS=1, build.py)
+# rfd_chamfer.h / rfd_eval.h / rfd_latent.h / rfd_loss.h / rfd_fit.h / rfd_render.h / rfd_decimate.h / rfd_simplify.h / rfd_fuse.h / rfd_sample.h / rfd_labels.h.  OPTIONAL marks the test hooks, which a deployment build (RFD_NO_TEST_HOOKS=1, build.py)
 # leaves out.
 OPTIONAL = "optional"
 ABI = {
@@ -123,6 +123,12 @@ ABI = {
     "rfd_sample_voxelize": (_i, [_i, _f, _i, _f, _f]),
     "rfd_sample_face_areas": (_i, [_i, _f, _f, _f]),
     "rfd_sample_surface": (_i, [_i, _i, _f, _f, _f, _f, _f, _f, _f]),
+    "rfd_labels_instance_aabb": (_i, [_i, _i, _i, _f, _f, _f, _f, _f]),
+    "rfd_labels_cad_extents": (_i, [_i, _i, _i, _f, _f, _f, _f, _f, _f, _f, _f]),
+    "rfd_labels_match_instances": (_i, [_i, _i, _f, _f, _f, _f, _f, _f]),
+    "rfd_labels_point_votes": (_i, [_i, _i, _i, _f, _f, _f, _f, _f]),
+    "rfd_labels_sample": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _d, _d, _fl, C.POINTER(C.c_double), _f, _f, _f, _f, _f,
+                               _f, _f, _f, _f]),
     "rfd_last_error_string": (C.c_char_p, []),
     "rfd_build_arch": (C.c_char_p, []),
     "rfd_device_status": (_i, []),

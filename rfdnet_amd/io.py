@@ -234,6 +234,45 @@ def read_mesh_ply(path, return_normals=False):
     return v, f
 
 
+_PLY_TYPES = {'char': 'i1', 'uchar': 'u1', 'short': 'i2', 'ushort': 'u2', 'int': 'i4', 'uint': 'u4', 'float': 'f4',
+              'double': 'f8', 'int8': 'i1', 'uint8': 'u1', 'int16': 'i2', 'uint16': 'u2', 'int32': 'i4', 'uint32': 'u4',
+              'float32': 'f4', 'float64': 'f8'}
+
+
+def read_scan_ply(path):
+    """-> (N,6) float32: x y z and red green blue (0 .. 255; zeros when the file has no colours) of the vertex element
+    of a PLY as scanners write it (ScanNet's *_vh_clean_2.ply: float xyz, uchar rgba), ascii or binary little endian.
+    The vertex element must come first and hold scalar properties only."""
+    with open(path, "rb") as fh:
+        data = fh.read()
+    end = data.index(b"end_header\n") + len(b"end_header\n")
+    head = [l.split() for l in data[:end].decode("ascii").split("\n") if l.strip()]
+    fmt = [l[1] for l in head if l[0] == "format"][0]
+    elements = [k for k, l in enumerate(head) if l[0] == "element"]
+    if not elements or head[elements[0]][1] != "vertex":
+        raise ValueError("%s: the vertex element must come first" % path)
+    nv = int(head[elements[0]][2])
+    props = [l for l in head[elements[0] + 1:(elements + [len(head)])[1]] if l[0] == "property"]
+    if any(l[1] == "list" for l in props):
+        raise ValueError("%s: a list property in the vertex element" % path)
+    names = [l[2] for l in props]
+    if fmt == "ascii":
+        rows = np.array([r.split() for r in data[end:].decode("ascii").split("\n")[:nv]], dtype=np.float64)
+        col = lambda name: rows[:, names.index(name)]
+    elif fmt == "binary_little_endian":
+        rec = np.frombuffer(data, dtype=[(l[2], '<' + _PLY_TYPES[l[1]]) for l in props], count=nv, offset=end)
+        col = lambda name: rec[name]
+    else:
+        raise ValueError("%s: format %s is not supported" % (path, fmt))
+    out = np.zeros((nv, 6), np.float32)
+    for k, name in enumerate(("x", "y", "z")):
+        out[:, k] = col(name)
+    if all(c in names for c in ("red", "green", "blue")):
+        for k, name in enumerate(("red", "green", "blue")):
+            out[:, 3 + k] = col(name)
+    return out
+
+
 def read_mesh(path):
     """a mesh file by its extension -> (vertices (V,3) float64, faces (F,3) int32): .off (colour columns dropped,
     polygons fanned from their first corner), .obj (read_obj) or .ply (read_mesh_ply, widened); else ValueError"""

@@ -67,6 +67,19 @@ class ScannetConfig(object):
             mean_size_arr = np.full((8, 3), 0.8)
         self.mean_size_arr = np.asarray(mean_size_arr, dtype=np.float64)
         assert self.mean_size_arr.shape == (self.num_size_cluster, 3), self.mean_size_arr.shape
+        # scannet_config.py:19-20: the reference's class ids (positions in its ShapeNet class list: table, chair,
+        # bookshelf, sofa, trash bin, cabinet, display, bathtub) -> the network's class 0 .. 7
+        self.class_ids = np.array([1, 7, 8, 13, 20, 31, 34, 43])
+        self.shapenetid2class = {int(class_id): i for i, class_id in enumerate(self.class_ids)}
+
+    def angle2class(self, angle):
+        """scannet_config.py:27-43: angle(s) in radians -> (heading bin as int16, residual) with
+        bin * (2 pi / N) + residual = angle mod 2 pi, the residual in [-pi / N, pi / N)"""
+        angle = np.asarray(angle, dtype=np.float64) % (2 * np.pi)
+        angle_per_class = 2 * np.pi / float(self.num_heading_bin)
+        shifted_angle = (angle + angle_per_class / 2) % (2 * np.pi)
+        class_id = np.int16(shifted_angle / angle_per_class)
+        return class_id, shifted_angle - (class_id * angle_per_class + angle_per_class / 2)
 
     def class2angle_cuda(self, pred_cls, residual, to_label_format=True):
         """scannet_config.py:55-63"""
