@@ -43,6 +43,9 @@ def build_parser():
                          "checkpoint with completion.encoder_latent.* to mean anything).  If it holds vote_label and "
                          "vote_label_mask, the loss dictionary of the reference's test mode is printed (detection loss; "
                          "with point_instance_labels and object_instance_labels also PointSeg's mask loss)")
+    ap.add_argument("--shapenet_path", type=str, default=None,
+                    help="--mode test with --gt: the directory of the ground-truth meshes (<catid>/<id>.off for the "
+                         "scan's shapenet_catids / shapenet_ids arrays); also prints the mesh AP / recall of the scene")
     ap.add_argument("--mean_size_npz", type=str, default=None,
                     help="class mean sizes (the reference's datasets/scannet/scannet_means.npz); default: "
                          "$RFD_MEAN_SIZE_NPZ or that path relative to the working directory")
@@ -120,7 +123,7 @@ def main():
         pc = synthetic.synthetic_scene(seed=args.synthetic if args.synthetic is not None else 10,
                                        n_points=cfg.config['data']['num_point'])
         data = {'point_clouds': torch.from_numpy(pc[None])}
-    data = {k: v.cuda() for k, v in data.items()}
+    data = {k: v.cuda() for k, v in data.items()}                       # (gt_meshes, a list, joins it below)
     torch.cuda.synchronize()
     t0 = time.time()
     records = None
@@ -139,7 +142,15 @@ def main():
             a = np.asarray(gt[k])
             per_scan = 2 if k == 'vote_label' else 1
             data[k] = torch.from_numpy(a[None] if a.ndim == per_scan else a).cuda()
-        end_points, ids, meshes, records = net.evaluate(data, completion=completion, losses=losses)
+        with_meshes = args.shapenet_path is not None
+        if with_meshes:
+            from rfdnet_amd.iscnet.mesh_eval import load_gt_meshes
+            if not all(k in gt.files for k in ('shapenet_catids', 'shapenet_ids')):
+                raise SystemExit("--shapenet_path needs shapenet_catids and shapenet_ids in the --gt file")
+            rows = np.nonzero(data['box_label_mask'][0].cpu().numpy() == 1)[0]
+            names = [np.asarray(gt[k]).reshape(-1)[rows] for k in ('shapenet_catids', 'shapenet_ids')]
+            data['gt_meshes'] = load_gt_meshes(args.shapenet_path, *names)
+        end_points, ids, meshes, records = net.evaluate(data, completion=completion, losses=losses, mesh=with_meshes)
     else:
         end_points, ids, meshes = net.generate(data, selection=args.selection)
     if args.post_processing and gt is None and len(meshes) and 'parsed_predictions' in end_points:
@@ -151,7 +162,8 @@ def main():
     print('Time elapsed: %s.' % (time.time() - t0))                       # demo.py:411
     if records is not None:
         from rfdnet_amd.iscnet.evaluation import APCalculator
-        calc = APCalculator((0.25, 0.5))
+        from rfdnet_amd.iscnet.mesh_eval import MeshAPCalculator
+        calc = (MeshAPCalculator if args.shapenet_path is not None else APCalculator)((0.25, 0.5))
         calc.step(records)
         for thr, metrics in zip((0.25, 0.5), calc.compute_metrics()):
             print('IoU %g: %s' % (thr, {k: float(v) for k, v in metrics.items()}))

@@ -80,9 +80,11 @@ class SceneRecords(object):
     buffer filled by one copy queued on the caller's stream.  The views score (B,C,K) f32, valid (B,C,K) u8,
     tp (nT,B,C,K) u8 and npos (B,C) i32 are meaningful once `event` has passed; compact() waits for it (and for
     nothing else) and returns the records as flat arrays
-    {'cls' (n) i32, 'score' (n) f32, 'tp' (nT,n) u8, 'npos' (C) i64, 'thr'}."""
+    {'cls' (n) i32, 'score' (n) f32, 'tp' (nT,n) u8, 'npos' (C) i64, 'thr'}.
+    mesh=True: the buffer carries a second flag array behind the first, tp_mesh (nT,B,C,K) u8 -- the same matching on the
+    mesh IoU (mesh_eval.py) -- and compact() has the extra key 'tp_mesh' (nT,n)."""
 
-    def __init__(self, thr, shape, buf, event, timing=None):
+    def __init__(self, thr, shape, buf, event, timing=None, mesh=False):
         B, C, K = shape
         n = B * C * K
         nT = len(thr)
@@ -92,6 +94,7 @@ class SceneRecords(object):
         o = 4 * n + 4 * B * C
         self.valid = buf[o:o + n].view(B, C, K)
         self.tp = buf[o + n:o + n + nT * n].view(nT, B, C, K)
+        self.tp_mesh = buf[o + n + nT * n:o + n + 2 * nT * n].view(nT, B, C, K) if mesh else None
         self.timing = timing                    # (start, end) events around the two launches, when asked for
         self._compact = None
 
@@ -107,13 +110,15 @@ class SceneRecords(object):
             self._compact = {'cls': ci.astype(np.int32), 'score': self.score.numpy()[bi, ci, ki],
                              'tp': self.tp.numpy()[:, bi, ci, ki], 'npos': self.npos.numpy().sum(0).astype(np.int64),
                              'thr': self.thr}
+            if self.tp_mesh is not None:
+                self._compact['tp_mesh'] = self.tp_mesh.numpy()[:, bi, ci, ki]
         return self._compact
 
 
 _thr_cache = _lib.ArtefactCache(64)      # the thresholds as an f64 device tensor, uploaded once per (device, thresholds)
 
 
-def _records(pred_corners, score, valid, gt_corners, gt_cls, gt_valid, thr, timing=False):
+def _records(pred_corners, score, valid, gt_corners, gt_cls, gt_valid, thr, timing=False, mesh_iou=None):
     """score (B,C,K) f32, valid (B,C,K) u8, gt_cls (B,G) i32, gt_valid (B,G) u8 on the device -> SceneRecords.
     Everything is queued on the current stream and the host waits for none of it: an argsort and a few small tensor
     kernels (ground-truth counts, packing), the two launches, and one device-to-host copy into pinned memory."""
@@ -131,23 +136,29 @@ def _records(pred_corners, score, valid, gt_corners, gt_cls, gt_valid, thr, timi
     tp = ap_match(iou3d, order, valid, gt_cls, gt_valid, thr_d)
     if ev:
         ev[1].record(stream)
+    flags = [tp.flatten()]
+    if mesh_iou is not None:                # the same matching -- order, validity, classes, thresholds -- on the mesh IoU
+        flags.append(ap_match(mesh_iou, order, valid, gt_cls, gt_valid, thr_d).flatten())
     npos = ((gt_cls.unsqueeze(1) == torch.arange(C, device=dev, dtype=gt_cls.dtype).view(1, C, 1)) &
             (gt_valid.unsqueeze(1) != 0)).sum(-1).int()
     packed = torch.cat([score.contiguous().view(torch.uint8).flatten(), npos.contiguous().view(torch.uint8).flatten(),
-                        valid.flatten(), tp.flatten()])
+                        valid.flatten()] + flags)
     buf = torch.empty(packed.shape, dtype=torch.uint8, pin_memory=True)
     buf.copy_(packed, non_blocking=True)
     done = torch.cuda.Event()
     done.record(stream)
-    return SceneRecords(thr, (B, C, K), buf, done, ev)
+    return SceneRecords(thr, (B, C, K), buf, done, ev, mesh=mesh_iou is not None)
 
 
 @torch.no_grad()
-def scene_records(eval_dict, parsed_predictions, parsed_gts, config=None, ap_iou_thresh=(0.25, 0.5), timing=False):
+def scene_records(eval_dict, parsed_predictions, parsed_gts, config=None, ap_iou_thresh=(0.25, 0.5), timing=False,
+                  mesh_iou=None):
     """Device tensors in (numpy is uploaded) -> SceneRecords, queued on the current stream; the host does not wait.
     A detection takes part iff pred_mask == 1 and obj_prob > conf_thresh.  per_class_proposal (default): it is scored
     for every class with sem_cls_probs[..., c] * obj_prob (a float32 product); otherwise once, for pred_sem_cls, with
-    obj_prob.  config: the eval config (predictions.DEFAULT_EVAL_CONFIG keys)."""
+    obj_prob.  config: the eval config (predictions.DEFAULT_EVAL_CONFIG keys).
+    mesh_iou: (B,K,G) f64, the mesh IoU of every (proposal, ground truth) pair (mesh_eval.scene_mesh_iou): the records
+    also carry 'tp_mesh', the flags of a second rfd_ap_match launch on it (eval_det.py:189-234 keeps the two side by side)."""
     cfg = dict(predictions.DEFAULT_EVAL_CONFIG)
     cfg.update(config or {})
     thr = _thresholds(ap_iou_thresh)
@@ -169,13 +180,18 @@ def scene_records(eval_dict, parsed_predictions, parsed_gts, config=None, ap_iou
     gt_corners = _lib.as_tensor(parsed_gts['gt_corners_3d_upright_camera'], dev, torch.float64)
     gt_cls = _lib.as_tensor(parsed_gts['sem_cls_label'], dev, torch.int32).contiguous()
     gt_valid = (_lib.as_tensor(parsed_gts['box_label_mask'], dev, torch.float32) == 1).to(torch.uint8).contiguous()
-    return _records(corners, score, valid.to(torch.uint8).contiguous(), gt_corners, gt_cls, gt_valid, thr, timing)
+    if mesh_iou is not None:
+        mesh_iou = _lib.as_tensor(mesh_iou, dev, torch.float64).contiguous()
+        if tuple(mesh_iou.shape) != (B, K, gt_cls.shape[1]):
+            raise ValueError("mesh_iou is %s, the scene has (B,K,G) = %s" % (tuple(mesh_iou.shape), (B, K, gt_cls.shape[1])))
+    return _records(corners, score, valid.to(torch.uint8).contiguous(), gt_corners, gt_cls, gt_valid, thr, timing, mesh_iou)
 
 
 def merge_records(records, thr=None, n_cls=0):
     """A list of records (SceneRecords or compact dicts; one record alone is a list of one) -> one compact dict
     {'cls' (n) i32, 'score' (n) f32, 'tp' (nT,n) u8, 'npos' (C) i64, 'thr'}.  An empty list needs `thr` and gives
-    n = 0 with n_cls zero counts."""
+    n = 0 with n_cls zero counts.  Records with 'tp_mesh' (nT,n) give a merged 'tp_mesh'; all of them have it or none
+    (ValueError)."""
     recs = [r.compact() if isinstance(r, SceneRecords) else r
             for r in (records if isinstance(records, (list, tuple)) else [records])]
     if thr is None:
@@ -189,10 +205,16 @@ def merge_records(records, thr=None, n_cls=0):
     for r in recs:
         npos[:len(r['npos'])] += np.asarray(r['npos'], np.int64)
     cat = lambda parts, empty: np.concatenate(parts, -1) if parts else empty
-    return {'cls': cat([np.asarray(r['cls'], np.int32) for r in recs], np.zeros(0, np.int32)),
+    with_mesh = [('tp_mesh' in r) for r in recs]
+    if any(with_mesh) and not all(with_mesh):
+        raise ValueError("records with and without mesh flags ('tp_mesh') cannot be merged")
+    out = {'cls': cat([np.asarray(r['cls'], np.int32) for r in recs], np.zeros(0, np.int32)),
             'score': cat([np.asarray(r['score'], np.float32) for r in recs], np.zeros(0, np.float32)),
             'tp': cat([np.asarray(r['tp'], np.uint8).reshape(len(thr), -1) for r in recs], np.zeros((len(thr), 0), np.uint8)),
             'npos': npos, 'thr': thr}
+    if any(with_mesh):
+        out['tp_mesh'] = np.concatenate([np.asarray(r['tp_mesh'], np.uint8).reshape(len(thr), -1) for r in recs], -1)
+    return out
 
 
 VOC07_RECALL_GRID = np.arange(11) * 0.1
@@ -221,7 +243,8 @@ class APCalculator(object):
 
     evaluate_mesh=True raises: the reference's mesh mAP voxelises every predicted and ground-truth mesh through the
     external `binvox` program and loads the ShapeNet ground-truth meshes from disk; neither is available to this
-    project, so the result could not be checked against anything."""
+    project, so the result could not be checked against anything.
+    mesh_eval.MeshAPCalculator computes mesh mAP on this project's own voxel grids instead."""
 
     def __init__(self, ap_iou_thresh=0.25, class2type_map=None, evaluate_mesh=False):
         if evaluate_mesh:
@@ -252,10 +275,11 @@ class APCalculator(object):
             raise ValueError("records were matched at other IoU thresholds than %r" % (self.ap_iou_thresh,))
         self.records.append(records)
 
-    def class_curves(self, ti, use_07_metric=True):
-        """-> {class: (rec, prec, ap)}; a class with ground truths and no prediction: (0, 0, 0) as in the reference"""
+    def class_curves(self, ti, use_07_metric=True, flags='tp'):
+        """-> {class: (rec, prec, ap)}; a class with ground truths and no prediction: (0, 0, 0) as in the reference.
+        flags: the record array the curves are drawn from ('tp', or 'tp_mesh' where the records have it)"""
         merged = merge_records(self.records, self.ap_iou_thresh)
-        cls, score, tp, npos = merged['cls'], merged['score'], merged['tp'][ti], merged['npos']
+        cls, score, tp, npos = merged['cls'], merged['score'], merged[flags][ti], merged['npos']
         n_cls = len(npos)
         out = {}
         for c in range(n_cls):
@@ -276,22 +300,23 @@ class APCalculator(object):
     def compute_metrics(self, use_07_metric=True):
         """use_07_metric=True is what the reference's compute_metrics_wo_mesh runs with (the default of
         eval_det_multiprocessing_wo_mesh); False gives the all-points AP."""
-        rets = []
-        for ti in range(len(self.ap_iou_thresh)):
-            cur = self.class_curves(ti, use_07_metric)
-            name = lambda c: self.class2type_map[c] if self.class2type_map else str(c)
-            ret = {}
-            for c in sorted(cur):
-                ret['%s Average Precision' % name(c)] = cur[c][2]
-            ret['mAP'] = np.mean([cur[c][2] for c in sorted(cur)]) if cur else float('nan')
-            rec_list = []
-            for c in sorted(cur):
-                r = cur[c][0][-1] if np.ndim(cur[c][0]) else 0
-                ret['%s Recall' % name(c)] = r
-                rec_list.append(r)
-            ret['AR'] = np.mean(rec_list) if cur else float('nan')
-            rets.append(ret)
+        rets = [self.metrics_of(self.class_curves(ti, use_07_metric)) for ti in range(len(self.ap_iou_thresh))]
         return rets[0] if self.single else rets
+
+    def metrics_of(self, cur, suffix=''):
+        """class_curves' result -> the reference's dict; suffix: '_mesh' for the mesh keys (ap_helper.py:108-122)"""
+        name = lambda c: self.class2type_map[c] if self.class2type_map else str(c)
+        ret = {}
+        for c in sorted(cur):
+            ret['%s Average Precision%s' % (name(c), suffix)] = cur[c][2]
+        ret['mAP' + suffix] = np.mean([cur[c][2] for c in sorted(cur)]) if cur else float('nan')
+        rec_list = []
+        for c in sorted(cur):
+            r = cur[c][0][-1] if np.ndim(cur[c][0]) else 0
+            ret['%s Recall%s' % (name(c), suffix)] = r
+            rec_list.append(r)
+        ret['AR' + suffix] = np.mean(rec_list) if cur else float('nan')
+        return ret
 
 
 def records_from_lists(batch_pred_map_cls, batch_gt_map_cls, ap_iou_thresh):

@@ -1,0 +1,277 @@
+"""Mesh mAP: per-object voxel grids and the mesh IoU of every (prediction, ground truth) pair on the device -- the
+counterpart of the mesh half of the reference's `--mode test` sweep:
+
+  voxelize_objects    batch_load_pred_data / batch_load_gt_data (net_utils/ap_helper.py:429-478) without binvox
+  mesh_iou            compute_mesh_iou (net_utils/eval_det.py:27-83), one call per pair over a process pool there
+  scene_mesh_iou      the mesh half of assembly_pred_map_cls / assembly_gt_map_cls (:267-323, :371-401)
+  MeshAPCalculator    compute_metrics_w_mesh (:84-122)
+  load_gt_meshes      the ShapeNet meshes of a scene's ground-truth rows (:380-384)
+
+The rules M1 - M5 are written out in include/rfd_mesh_eval.h and restated in numpy in tests/mesh_iou_f64.py; the
+kernels are csrc/mesh_iou.hip.  Everything downstream of the voxel grids returns the reference's own results
+(tests/golden/F_MIOU.npz); the grids themselves are this project's contract.
+
+Deviations from the reference: the surface and interior grids of mesh_sample (pinned to the reference's libmesh /
+voxels libraries) stand in for binvox's `exact` and `wireframe + dilated_carving` grids -- binvox is an external
+program and its carving is not reproduced; a world point is looked up with `floor`, not trimesh's `round` about the
+voxel centre (they differ only exactly on a cell boundary); a detection that takes part but has no mesh has mesh IoU 0
+with everything, where the reference raises ValueError.
+
+Each object is voxelised on its own by the existing voxelisers, which costs a few host synchronisations per object
+(MeshIntersector); tools/mesh_eval_cost.py measures them beside the pack and the IoU kernel.
+"""
+import os
+
+import numpy as np
+import torch
+
+from .. import _lib, mesh_sample
+from . import scene as scene_module
+from .evaluation import APCalculator
+from .generator import Mesh
+
+VOXEL_SIZE = 0.047       # ap_helper.py:267, :371
+MAX_DIM = 256
+MAX_PRED, MAX_GT = 1024, 256     # rfd_ap_match's limits
+
+
+def object_frame(lo, hi, voxel_size=VOXEL_SIZE):
+    """Rule M1 on the host, float64: the per-axis extent lo, hi (3,) of an object's placed vertices ->
+    (lo (3,) f64, L, cell, D), or None where the object has no grid (L not finite or 0).  D > 256: ValueError."""
+    lo, hi = np.asarray(lo, np.float64), np.asarray(hi, np.float64)
+    with np.errstate(invalid='ignore', over='ignore'):
+        L = np.max(hi - lo)
+    if not np.isfinite(L) or L == 0:
+        return None
+    D = max(int(L / voxel_size), 2)
+    if D > MAX_DIM:
+        raise ValueError("mesh IoU: an object of extent %g needs a %d^3 grid at voxel size %g; at most %d^3"
+                         % (L, D, voxel_size, MAX_DIM))
+    return lo, float(L), float(L / D), D
+
+
+def words_of(D):
+    return D * D * ((D + 63) // 64)
+
+
+class ObjectGrids(object):
+    """The object table of include/rfd_mesh_eval.h plus the packed words, on one device: frame (N,4) f64 (lo, cell),
+    dim (N) i32 (0: no grid), off (N) i64, cnt (N,2) i32 (|U|, |S|), words (n_words) i64 (the bit words).  `dims` is
+    the host's copy of dim."""
+
+    def __init__(self, frame, dim, off, cnt, words, dims):
+        self.frame, self.dim, self.off, self.cnt, self.words, self.dims = frame, dim, off, cnt, words, dims
+
+    def __len__(self):
+        return len(self.dims)
+
+    @property
+    def n_words(self):
+        return int(self.words.numel())
+
+    @property
+    def device(self):
+        return self.words.device
+
+
+@torch.no_grad()
+def pack_grids(objects, device):
+    """objects: per object None (no grid) or (S, I, lo, cell) with S, I (D,D,D) bool / u8 tensors on `device` (or
+    numpy), lo (3,) and cell floats -> ObjectGrids: one rfd_objgrid_pack launch per object into one shared buffer."""
+    device = torch.device(device)
+    N = len(objects)
+    dims = np.zeros(N, np.int32)
+    frame = np.zeros((N, 4), np.float64)
+    off = np.zeros(N, np.int64)
+    total = 0
+    for i, o in enumerate(objects):
+        if o is None:
+            continue
+        S, I, lo, cell = o
+        D = int(S.shape[0])
+        if tuple(S.shape) != (D, D, D) or tuple(I.shape) != (D, D, D):
+            raise ValueError("pack_grids: S and I are (D,D,D), got %s and %s" % (tuple(S.shape), tuple(I.shape)))
+        if D > MAX_DIM:
+            raise ValueError("pack_grids: D = %d, at most %d" % (D, MAX_DIM))
+        dims[i], off[i] = D, total
+        frame[i, :3], frame[i, 3] = np.asarray(lo, np.float64), float(cell)
+        total += words_of(D)
+    words = torch.zeros(max(total, 1), dtype=torch.int64, device=device)
+    cnt = torch.zeros(N, 2, dtype=torch.int32, device=device)
+    for i, o in enumerate(objects):
+        if o is None:
+            continue
+        S = _lib.as_tensor(o[0], device, torch.uint8).contiguous()
+        I = _lib.as_tensor(o[1], device, torch.uint8).contiguous()
+        _lib.call("rfd_objgrid_pack", device, int(dims[i]), S.data_ptr(), I.data_ptr(), words.data_ptr(), int(off[i]),
+                  int(words.numel()), cnt[i].data_ptr())
+    up = lambda a: torch.from_numpy(a).to(device)
+    return ObjectGrids(up(frame), up(dims), up(off), cnt, words, dims)
+
+
+@torch.no_grad()
+def object_grids(scene_mesh, voxel_size=VOXEL_SIZE):
+    """Rules M1 and M2 for every object of a SceneMesh -> the list pack_grids takes: None or (S, I, lo, cell).
+    One read-back for all frames, then per object the two voxelisers of mesh_sample."""
+    _lib.need_gpu(scene_mesh.vertices)
+    dev = scene_mesh.vertices.device
+    obj_off = scene_mesh.obj_off.cpu().numpy().astype(np.int64)
+    face_off = scene_mesh.face_off.cpu().numpy().astype(np.int64)
+    N = len(obj_off) - 1
+    if N == 0:
+        return []
+    v = scene_mesh.vertices.double()
+    seg = torch.repeat_interleave(torch.arange(N, device=dev), torch.from_numpy(np.diff(obj_off)).to(dev))
+    idx = seg[:, None].expand(-1, 3)
+    # amin / amax let a NaN through (an object of zero extent is NaN after the placement): it then has no grid
+    lo = torch.full((N, 3), np.inf, dtype=torch.float64, device=dev).scatter_reduce(0, idx, v, 'amin')
+    hi = torch.full((N, 3), -np.inf, dtype=torch.float64, device=dev).scatter_reduce(0, idx, v, 'amax')
+    L = (hi - lo).amax(1)
+    unit = (v - lo[seg]) / L[seg, None] - 0.5                                      # M2's map, for all objects at once
+    # the extent of what the faces reference, in the unit cube: a flat object has no interior (and the intersector
+    # refuses it)
+    faces = scene_mesh.faces.long()
+    fobj = scene_mesh.face_obj.long()[:, None, None].expand(-1, 3, 3).reshape(-1, 3)
+    corner = unit[faces.clamp(0, max(int(v.shape[0]) - 1, 0))].reshape(-1, 3) if faces.numel() else unit[:0]
+    tlo = torch.full((N, 3), np.inf, dtype=torch.float64, device=dev).scatter_reduce(0, fobj, corner, 'amin')
+    thi = torch.full((N, 3), -np.inf, dtype=torch.float64, device=dev).scatter_reduce(0, fobj, corner, 'amax')
+    host = torch.cat([lo, hi, tlo, thi], 1).cpu().numpy()
+    out = []
+    for k in range(N):
+        n_f = int(face_off[k + 1] - face_off[k])
+        fr = object_frame(host[k, 0:3], host[k, 3:6], voxel_size) if obj_off[k + 1] > obj_off[k] and n_f else None
+        if fr is None:
+            out.append(None)
+            continue
+        lo_k, _, cell, D = fr
+        vk = unit[obj_off[k]:obj_off[k + 1]]
+        fk = faces[face_off[k]:face_off[k + 1]] - int(obj_off[k])
+        S = mesh_sample.voxelize_surface(vk, fk, D)
+        if (host[k, 9:12] - host[k, 6:9] > 0).all():
+            centres = mesh_sample.grid_points(D, torch.zeros(1, 3, dtype=torch.float64, device=dev))   # no jitter
+            I = mesh_sample.check_mesh_contains(vk, fk, centres).reshape(D, D, D)
+        else:
+            I = torch.zeros_like(S)
+        out.append((S, I, lo_k, cell))
+    return out
+
+
+def voxelize_objects(scene_mesh, voxel_size=VOXEL_SIZE):
+    """SceneMesh (scene.place_objects / place_in_corners) -> ObjectGrids, one row per object"""
+    return pack_grids(object_grids(scene_mesh, voxel_size), scene_mesh.vertices.device)
+
+
+def _check_counts(P, G):
+    if P > MAX_PRED or G > MAX_GT:
+        raise ValueError("mesh IoU: %d predictions x %d ground truths; at most %d x %d" % (P, G, MAX_PRED, MAX_GT))
+
+
+@torch.no_grad()
+def mesh_iou_counts(pred_grids, gt_grids):
+    """-> counts (P,G,2) i32 on the device: a_AB, a_BA of every pair (one rfd_mesh_iou_counts launch)"""
+    P, G = len(pred_grids), len(gt_grids)
+    dev = pred_grids.device
+    counts = torch.zeros(P, G, 2, dtype=torch.int32, device=dev)
+    a, b = pred_grids, gt_grids
+    _lib.call("rfd_mesh_iou_counts", dev, P, G, a.frame.data_ptr(), a.dim.data_ptr(), a.off.data_ptr(),
+              a.words.data_ptr(), a.n_words, b.frame.data_ptr(), b.dim.data_ptr(), b.off.data_ptr(), b.words.data_ptr(),
+              b.n_words, counts.data_ptr())
+    return counts
+
+
+@torch.no_grad()
+def scatter_iou(pred_grids, gt_grids, counts, iou, rows_p=None, rows_g=None):
+    """Rule M5 into iou (K,G') f64 at (rows_p[p], rows_g[g]) (None: the identity); one rfd_mesh_iou_finalize launch"""
+    dev = iou.device
+    as_rows = lambda r: None if r is None else _lib.as_tensor(r, dev, torch.int32).contiguous()
+    rows_p, rows_g = as_rows(rows_p), as_rows(rows_g)
+    _lib.call("rfd_mesh_iou_finalize", dev, len(pred_grids), len(gt_grids), counts.data_ptr(), pred_grids.cnt.data_ptr(),
+              gt_grids.cnt.data_ptr(), _lib.ptr(rows_p), _lib.ptr(rows_g), iou.shape[0], iou.shape[1], iou.data_ptr())
+    return iou
+
+
+def mesh_iou(pred_grids, gt_grids):
+    """-> (iou (P,G) f64, counts (P,G,2) i32) on the device"""
+    counts = mesh_iou_counts(pred_grids, gt_grids)
+    iou = torch.zeros(len(pred_grids), len(gt_grids), dtype=torch.float64, device=counts.device)
+    return scatter_iou(pred_grids, gt_grids, counts, iou), counts
+
+
+def _on(a, device, dtype):
+    """a tensor as it is (its own float / integer type), anything else through numpy as `dtype`, on `device`"""
+    return a.to(device) if torch.is_tensor(a) else torch.as_tensor(np.asarray(a)).to(device, dtype)
+
+
+def _as_mesh(m, device):
+    if m is None:
+        return Mesh(torch.zeros(0, 3, dtype=torch.float64, device=device), torch.zeros(0, 3, dtype=torch.int64, device=device))
+    v, f = (m.vertices, m.faces) if hasattr(m, 'vertices') else m
+    return Mesh(_on(v, device, torch.float64), _on(f, device, torch.int64))
+
+
+@torch.no_grad()
+def scene_mesh_iou(meshes, proposal_ids, parsed_predictions, parsed_gts, gt_meshes, voxel_size=VOXEL_SIZE):
+    """The mesh IoU matrix of ONE scene (the reference asserts bsize == 1 too) -> (1,K,G) f64 on the device, what
+    evaluation.scene_records takes as `mesh_iou`.
+    meshes, proposal_ids: the generated meshes and their proposals (ISCNet.generate); they are placed in
+    parsed_predictions['pred_corners_3d_upright_camera'] (1,K,8,3), the boxes that are scored.
+    gt_meshes: one (vertices, faces) (or an object with these attributes) per ground-truth row with
+    box_label_mask == 1, in row order; None for a missing mesh.  They are placed in the ground-truth corners.
+    A proposal without a generated mesh, and a ground truth without one, keep IoU 0 with everything."""
+    corners = parsed_predictions['pred_corners_3d_upright_camera']
+    _lib.need_gpu(corners)
+    dev = corners.device
+    if corners.shape[0] != 1:
+        raise ValueError("mesh IoU runs on one scene at a time, got a batch of %d" % corners.shape[0])
+    K = corners.shape[1]
+    gt_corners = _lib.as_tensor(parsed_gts['gt_corners_3d_upright_camera'], dev, torch.float64)
+    G = gt_corners.shape[1]
+    iou = torch.zeros(1, K, G, dtype=torch.float64, device=dev)
+    rows_g = torch.nonzero(_lib.as_tensor(parsed_gts['box_label_mask'], dev, torch.float32)[0] == 1)[:, 0]
+    if len(gt_meshes) != rows_g.numel():
+        raise ValueError("gt_meshes: %d meshes for %d ground-truth boxes" % (len(gt_meshes), rows_g.numel()))
+    ids = proposal_ids.reshape(-1).to(dev) if torch.is_tensor(proposal_ids) else \
+        torch.as_tensor(np.asarray(proposal_ids).reshape(-1), device=dev)
+    _check_counts(int(ids.numel()), int(rows_g.numel()))
+    if ids.numel() == 0 or rows_g.numel() == 0:
+        return iou
+    pred = scene_module.place_objects([_as_mesh(m, dev) for m in meshes], ids.view(1, -1, 1), parsed_predictions)
+    gt_cls = _lib.as_tensor(parsed_gts['sem_cls_label'], dev, torch.int32)[0][rows_g]
+    gt = scene_module.place_in_corners([_as_mesh(m, dev) for m in gt_meshes], gt_corners[0][rows_g], gt_cls)
+    pg, gg = voxelize_objects(pred, voxel_size), voxelize_objects(gt, voxel_size)
+    scatter_iou(pg, gg, mesh_iou_counts(pg, gg), iou[0], ids, rows_g)
+    return iou
+
+
+class MeshAPCalculator(APCalculator):
+    """compute_metrics_w_mesh (ap_helper.py:84-122) on records with mesh flags (scene_records(mesh_iou=...)):
+    compute_metrics() returns the box dict of APCalculator plus '<cls> Average Precision_mesh', 'mAP_mesh',
+    '<cls> Recall_mesh', 'AR_mesh' from the same curve code on 'tp_mesh'."""
+
+    def __init__(self, ap_iou_thresh=0.25, class2type_map=None):
+        super(MeshAPCalculator, self).__init__(ap_iou_thresh, class2type_map)
+        self.evaluate_mesh = True
+
+    def compute_metrics(self, use_07_metric=True):
+        """VOC07 by default, as eval_det_multiprocessing_w_mesh has it"""
+        from .evaluation import merge_records
+        if self.records and 'tp_mesh' not in merge_records(self.records, self.ap_iou_thresh):
+            raise ValueError("MeshAPCalculator: the records carry no mesh flags (scene_records(mesh_iou=...))")
+        flags = 'tp_mesh' if self.records else 'tp'
+        rets = []
+        for ti in range(len(self.ap_iou_thresh)):
+            ret = self.metrics_of(self.class_curves(ti, use_07_metric))
+            ret.update(self.metrics_of(self.class_curves(ti, use_07_metric, flags), '_mesh'))
+            rets.append(ret)
+        return rets[0] if self.single else rets
+
+
+def load_gt_meshes(shapenet_path, catids, ids):
+    """<shapenet_path>/<catid>/<id>.off for every ground-truth row -> [(vertices (V,3) f64, faces (F,3) i32 numpy)];
+    None for a file that does not exist"""
+    from ..io import read_mesh
+    out = []
+    for cat, name in zip(catids, ids):
+        path = os.path.join(shapenet_path, str(cat), str(name) + '.off')
+        out.append(read_mesh(path) if os.path.exists(path) else None)
+    return out

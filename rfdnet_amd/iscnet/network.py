@@ -202,7 +202,7 @@ class ISCNet(nn.Module):
         return total_loss
 
     def evaluate(self, data, fit=True, ap_iou_thresh=(0.25, 0.5), timing=False, completion=False, completion_eps=None,
-                 losses=False):
+                 losses=False, mesh=False, voxel_size=None):
         """The tail of the reference's `generate` in test mode (network.py:85-177): detection and completion with
         selection='nms', then (fit: True or 'autograd', or 'device' for the ragged loop of csrc/fit_pose.hip; False for
         none) the box refinement of fit_mesh_to_scan, then the evaluation records of the --
@@ -220,7 +220,14 @@ class ISCNet(nn.Module):
         losses=True adds the loss dictionary the reference prints beside the metrics (testing.py:63-68): `data` also
         carries vote_label (B,N,9) and vote_label_mask (B,N), and for the mask loss point_instance_labels (B,N) and
         object_instance_labels (B,G) (absent: mask loss 0).  end_points['loss'] = ISCNet.loss(...): DetectionLoss's thirteen
-        keys, completion_loss, mask_loss, and `total` with ONet_Loss's weight * (completion + 100 mask) added."""
+        keys, completion_loss, mask_loss, and `total` with ONet_Loss's weight * (completion + 100 mask) added.
+        mesh=True adds the mesh half of the reference's evaluation (ap_helper.py:267-323, :371-401; one scene, as its
+        `assert bsize == 1`): the generated meshes are placed in the boxes that are scored (after fit_mesh_to_scan if it
+        ran), the ground-truth meshes data['gt_meshes'] -- one (vertices, faces) per ground-truth row with box_label_mask
+        == 1, None for a missing mesh -- in the ground-truth boxes, both sides are voxelised (voxel_size: 0.047) and the
+        mesh IoU of every pair (mesh_eval.scene_mesh_iou, kept in end_points['mesh_iou'] (1,K,G)) is matched like the box
+        IoU: the records carry 'tp_mesh' for mesh_eval.MeshAPCalculator.  A detection that takes part but has no mesh
+        has mesh IoU 0 with everything (the reference raises ValueError there)."""
         from . import evaluation, fit as fit_module
         method = fit_module.fit_method(fit)
         captured = {}
@@ -242,8 +249,13 @@ class ISCNet(nn.Module):
                                            method=method)
             end_points['parsed_predictions'] = parsed
         parsed_gts = evaluation.parse_groundtruths(data, self.cfg.dataset_config)
+        mesh_iou = None
+        if mesh:
+            from . import mesh_eval
+            mesh_iou = end_points['mesh_iou'] = mesh_eval.scene_mesh_iou(
+                meshes, ids, parsed, parsed_gts, data['gt_meshes'], voxel_size or mesh_eval.VOXEL_SIZE)
         records = evaluation.scene_records(eval_dict, parsed, parsed_gts, getattr(self.cfg, 'eval_overrides', None),
-                                           ap_iou_thresh, timing=timing)
+                                           ap_iou_thresh, timing=timing, mesh_iou=mesh_iou)
         return end_points, ids, meshes, records
 
     @torch.no_grad()

@@ -1,5 +1,6 @@
 """place_objects: the generated meshes, each in its predicted box, in the scan's frame -- the first half of the
-reference's `visualize` (demo.py:329-377; the second half, the picture, is rfdnet_amd/render.py).
+reference's `visualize` (demo.py:329-377; the second half, the picture, is rfdnet_amd/render.py); place_in_corners: the
+same placement for given boxes (the reference's fit_shapenet_obj_to_votenet_box, ap_helper.py:404-426, is the same six steps).
 
 The decoder leaves every mesh in its canonical cube.  The reference reads the meshes back from their files and, per
 object (demo.py:351-360), in float64:
@@ -49,18 +50,35 @@ def place_objects(meshes, proposal_ids, parsed_predictions, with_normals=False):
     K = len(meshes)
     if len(ids) != K:
         raise ValueError("place_objects: %d meshes for %d proposal ids" % (K, len(ids)))
-    as_t = lambda a: a if torch.is_tensor(a) else torch.as_tensor(np.asarray(a))
-    verts = [as_t(m.vertices).reshape(-1, 3) for m in meshes]
-    faces = [as_t(m.faces).reshape(-1, 3) for m in meshes]
     corners_all = parsed_predictions['pred_corners_3d_upright_camera']
-    dev = verts[0].device if K else corners_all.device if torch.is_tensor(corners_all) else torch.device('cpu')
-    n_v = np.asarray([v.shape[0] for v in verts], np.int64)
-    n_f = np.asarray([f.shape[0] if v.shape[0] else 0 for v, f in zip(verts, faces)], np.int64)
-    obj_off, face_off = ragged.offsets(n_v), ragged.offsets(n_f)
+    dev = _mesh_device(meshes, corners_all)
     sem = parsed_predictions.get('pred_sem_cls')
     rows = torch.from_numpy(ids).to(dev)
     obj_class = torch.zeros(K, dtype=torch.int32, device=dev) if sem is None else \
         _lib.as_tensor(sem, dev, torch.int64)[0][rows].to(torch.int32)
+    corners = _lib.as_tensor(corners_all, dev, torch.float64)[0][rows]
+    return place_in_corners(meshes, corners, obj_class, with_normals)
+
+
+_as_t = lambda a: a if torch.is_tensor(a) else torch.as_tensor(np.asarray(a))
+
+
+def _mesh_device(meshes, corners):
+    return _as_t(meshes[0].vertices).device if len(meshes) else corners.device if torch.is_tensor(corners) else torch.device('cpu')
+
+
+def place_in_corners(meshes, corners, obj_class, with_normals=False):
+    """The placement itself, for given boxes: meshes as for place_objects, corners (K',8,3): the box of every mesh (upright
+    camera frame), obj_class (K') -> SceneMesh on the meshes' device.  place_objects places the generated meshes in their
+    predicted boxes with it, mesh_eval the ground-truth meshes in the ground-truth boxes."""
+    K, as_t = len(meshes), _as_t
+    verts = [as_t(m.vertices).reshape(-1, 3) for m in meshes]
+    faces = [as_t(m.faces).reshape(-1, 3) for m in meshes]
+    dev = _mesh_device(meshes, corners)
+    obj_class = _lib.as_tensor(obj_class, dev, torch.int32)
+    n_v = np.asarray([v.shape[0] for v in verts], np.int64)
+    n_f = np.asarray([f.shape[0] if v.shape[0] else 0 for v, f in zip(verts, faces)], np.int64)
+    obj_off, face_off = ragged.offsets(n_v), ragged.offsets(n_f)
     out = SceneMesh(obj_off=ragged.to_int32(obj_off, dev), face_off=ragged.to_int32(face_off, dev), obj_class=obj_class,
                     normals=None)
     if obj_off[-1] == 0:
@@ -71,7 +89,7 @@ def place_objects(meshes, proposal_ids, parsed_predictions, with_normals=False):
             out.normals = torch.zeros(0, 3, dtype=torch.float32, device=dev)
         return out
 
-    corners = _lib.as_tensor(corners_all, dev, torch.float64)[0][rows]
+    corners = _lib.as_tensor(corners, dev, torch.float64)
     centre, sizes, theta = box_params_from_corners(corners)
     seg = torch.from_numpy(ragged.owners(n_v)).to(dev)
     v = torch.cat([x.to(dev, torch.float64) for x in verts])

@@ -352,7 +352,9 @@ def gather_records(records, dist=None, device=None, thr=None):
     the IoU thresholds (`thr`).  Each rank packs its own into a float64 vector [n, C, npos (C), n x (class, score, tp
     bits)] padded to the job's maximum (one all_reduce(MAX) of the two sizes) and ONE all_gather moves them; float32
     scores survive the trip through float64 exactly.  device: where the collectives' tensors live (default: the CPU
-    under gloo, else the current GPU).  dist=None or not initialised => the merged records, no communication."""
+    under gloo, else the current GPU).  dist=None or not initialised => the merged records, no communication.
+    Records with mesh flags ('tp_mesh', iscnet.mesh_eval) keep them: their bits travel above the box flags' in the same
+    column, and a rank without records learns from the size exchange that the job carries them."""
     import numpy as np
     from .iscnet.evaluation import merge_records
     rec = merge_records(records, thr)
@@ -361,9 +363,15 @@ def gather_records(records, dist=None, device=None, thr=None):
     if device is None:
         device = torch.device("cpu") if dist.get_backend() == "gloo" else torch.device("cuda", torch.cuda.current_device())
     n, n_cls, n_thr = len(rec['cls']), len(rec['npos']), len(rec['thr'])
-    sizes = torch.tensor([n, n_cls], dtype=torch.int64, device=device)
+    mesh = 'tp_mesh' in rec
+    sizes = torch.tensor([n, n_cls, int(mesh)], dtype=torch.int64, device=device)
     dist.all_reduce(sizes, op=dist.ReduceOp.MAX)
     n_max, c_max = int(sizes[0]), int(sizes[1])
+    if int(sizes[2]) and not mesh:
+        if n:
+            raise ValueError("records with and without mesh flags ('tp_mesh') cannot be merged")
+        rec = dict(rec, tp_mesh=np.zeros((n_thr, 0), np.uint8))
+        mesh = True
     vec = np.zeros(2 + c_max + 3 * n_max)
     vec[0], vec[1] = n, n_cls
     vec[2:2 + n_cls] = rec['npos']
@@ -371,6 +379,8 @@ def gather_records(records, dist=None, device=None, thr=None):
     body[:n, 0] = rec['cls']
     body[:n, 1] = rec['score']
     body[:n, 2] = (rec['tp'].astype(np.int64) << np.arange(n_thr)[:, None]).sum(0)
+    if mesh:
+        body[:n, 2] += (rec['tp_mesh'].astype(np.int64) << (n_thr + np.arange(n_thr))[:, None]).sum(0)
     mine = torch.from_numpy(vec).to(device)
     world = dist.get_world_size()
     out = torch.empty(world * mine.numel(), dtype=torch.float64, device=device)
@@ -384,4 +394,6 @@ def gather_records(records, dist=None, device=None, thr=None):
         parts.append({'cls': b[:, 0].astype(np.int32), 'score': b[:, 1].astype(np.float32),
                       'tp': ((bits[None, :] >> np.arange(n_thr)[:, None]) & 1).astype(np.uint8),
                       'npos': row[2:2 + c].astype(np.int64), 'thr': rec['thr']})
+        if mesh:
+            parts[-1]['tp_mesh'] = ((bits[None, :] >> (n_thr + np.arange(n_thr))[:, None]) & 1).astype(np.uint8)
     return merge_records(parts, rec['thr'])

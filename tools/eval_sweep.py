@@ -16,6 +16,9 @@ With seeded weights the mAP is near zero: the tool then exists for the path and 
 samples and 16^3 voxels of the ground-truth cuboids (synthetic.object_occupancy): the mean completion loss and voxel IoU
 go into the line as "completion".  It attaches the latent encoder before the weights are seeded, which shifts the
 seeded completion weights: the other figures of such a run are not comparable with a run without the flag.
+--mesh (synthetic scenes) adds mesh mAP: the ground-truth mesh of a box is a unit cube (12 faces) placed in the box,
+ISCNet.evaluate(mesh=True) voxelises it and the generated meshes, and "mAP_mesh@..." / "AR_mesh@..." join the line.  The
+timed legs then include the mesh stage ("scenes_per_s_with_eval").
 With --gpus M the scenes are dealt round robin to M processes (sharding.launch_local_ranks) and the records meet in
 one all_gather (sharding.gather_records); throughput is all scenes over the slowest rank.
 """
@@ -57,6 +60,11 @@ def labels_from_boxes(boxes, cls, dataset_config, max_obj=64):
     return out
 
 
+CUBE_VERTICES = np.array([[x, y, z] for x in (0., 1.) for y in (0., 1.) for z in (0., 1.)])
+CUBE_FACES = np.array([[0, 1, 3], [0, 3, 2], [4, 6, 7], [4, 7, 5], [0, 4, 5], [0, 5, 1], [2, 3, 7], [2, 7, 6], [0, 2, 6],
+                       [0, 6, 4], [1, 5, 7], [1, 7, 3]])
+
+
 def load_scene(args, i, cfg, files):
     from rfdnet_amd import synthetic
     if files:
@@ -74,7 +82,10 @@ def load_scene(args, i, cfg, files):
                             synthetic.object_occupancy(boxes, seed=args.seed + i)):
                 data[k] = np.zeros((1, max_obj) + a.shape[1:], np.float32)
                 data[k][0, :len(boxes)] = a
-    return {k: torch.from_numpy(v).cuda() for k, v in data.items()}
+    out = {k: torch.from_numpy(v).cuda() for k, v in data.items()}
+    if getattr(args, 'mesh', False):
+        out['gt_meshes'] = [(CUBE_VERTICES, CUBE_FACES)] * int((data['box_label_mask'][0] == 1).sum())
+    return out
 
 
 def main():
@@ -93,8 +104,12 @@ def main():
                     help="fit_mesh_to_scan's method: the padded autograd loop (default) or the ragged loop on the device")
     ap.add_argument("--completion", action="store_true",
                     help="synthetic scenes, --gpus 1: also report the completion loss and the voxel IoU")
+    ap.add_argument("--mesh", action="store_true",
+                    help="synthetic scenes: also report mesh mAP / AR against unit-cube ground-truth meshes")
     ap.add_argument("--out", type=str, default=os.path.join(ROOT, "profiles", "eval_stage.json"))
     args = ap.parse_args()
+    if args.mesh and args.gt:
+        ap.error("--mesh runs on synthetic scenes (their ground-truth meshes are unit cubes)")
     if args.completion and (args.gt or args.gpus > 1):
         ap.error("--completion runs on synthetic scenes in one process")
 
@@ -149,10 +164,10 @@ def main():
 
     records, stage_ms, t_off, t_on = [], [], 0.0, 0.0
     if mine:                                                              # warm-up: caches, packed weights, allocator
-        net.evaluate(load_scene(args, mine[0], cfg, files), fit=fit, ap_iou_thresh=thr)[3].compact()
+        net.evaluate(load_scene(args, mine[0], cfg, files), fit=fit, ap_iou_thresh=thr, mesh=args.mesh)[3].compact()
     for n, i in enumerate(mine):
         data = load_scene(args, i, cfg, files)
-        with_eval = lambda d: net.evaluate(d, fit=fit, ap_iou_thresh=thr, timing=True)[3]
+        with_eval = lambda d: net.evaluate(d, fit=fit, ap_iou_thresh=thr, timing=True, mesh=args.mesh)[3]
         if n % 2:                                                         # the leg that goes first alternates
             rec, dt_on = timed(with_eval, data)
             _, dt_off = timed(without_eval, data)
@@ -182,7 +197,9 @@ def main():
         times = mine_t.view(1, 4).cpu().numpy()
     gathered = sharding.gather_records(records, dist, thr=thr)
     if rank == 0:
-        calc = evaluation.APCalculator(thr)
+        if args.mesh:
+            from rfdnet_amd.iscnet.mesh_eval import MeshAPCalculator
+        calc = MeshAPCalculator(thr) if args.mesh else evaluation.APCalculator(thr)
         calc.step(gathered)
         t0 = time.perf_counter()
         m25, m50 = calc.compute_metrics()
@@ -199,6 +216,9 @@ def main():
                 "eval_stage_device_ms_per_scene": float(times[:, 3].sum() / steps) if steps else None,
                 "compute_metrics_host_s": host_s,
                 "scenes_per_s_without_eval": rate(1), "scenes_per_s_with_eval": rate(2)}
+        if args.mesh:
+            line.update({"mAP_mesh@0.25": num(m25)['mAP_mesh'], "AR_mesh@0.25": num(m25)['AR_mesh'],
+                         "mAP_mesh@0.5": num(m50)['mAP_mesh'], "AR_mesh@0.5": num(m50)['AR_mesh']})
         if completion is not None:
             line["completion"] = completion
         text = json.dumps(line)
