@@ -6,7 +6,8 @@
 // sorts, unique, prefix sums) is the host module's; what is here is one thread per vertex / face / run, and for the hot
 // kernel sixteen lanes per cell: lane j adds the cell's corners j, j + 16, ... in order and a halving tree of wave
 // shuffles adds the sixteen partial sums, the same shape at every grid size and in every batch.  No atomics at all.
-#include "common.h"
+// The mesh of an item, the f64 helpers and rule 5's kernel are mesh_batch.h's, shared with mesh_simplify.hip.
+#include "mesh_batch.h"
 #include "../../include/rfd_decimate.h"
 
 namespace {
@@ -15,29 +16,6 @@ constexpr int DEC_THREADS = 256;
 constexpr int CELL_LANES = 16;                         // partial sums of a cell (rule 3)
 constexpr int CELLS_PER_BLOCK = DEC_THREADS / CELL_LANES;
 constexpr int MAX_CELLS = 1290;                        // 1290^3 < 2^31 <= 1291^3
-
-// the segment of item i: the last k with off[k] <= i (empty segments repeat an offset); 0 <= i < off[K]
-__device__ __forceinline__ int segment_of(const int *__restrict__ off, int K, int i) {
-  int lo = 0, hi = K;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (off[mid] <= i) lo = mid; else hi = mid;
-  }
-  return lo;
-}
-
-__device__ __forceinline__ bool finite_f64(double v) { return (__double2hiint(v) & 0x7ff00000) != 0x7ff00000; }
-
-struct D3 {
-  double x, y, z;
-};
-template <typename T>
-__device__ __forceinline__ D3 ld3(const void *__restrict__ p, size_t i) {
-  const T *q = static_cast<const T *>(p) + i * 3;
-  return {(double)q[0], (double)q[1], (double)q[2]};
-}
-__device__ __forceinline__ D3 sub(D3 a, D3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ double dot(D3 a, D3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
 
 // rule 1: clamp(floor((x - lo) * inv_h), 0, cells - 1), decided in f64 before the conversion to an integer
 __device__ __forceinline__ int cell_index(double x, double lo, double inv_h, int cells) {
@@ -153,12 +131,8 @@ __global__ __launch_bounds__(DEC_THREADS) void cell_solve_kernel(
     if ((unsigned)i0 >= (unsigned)nv || (unsigned)i1 >= (unsigned)nv || (unsigned)i2 >= (unsigned)nv) continue;
     const D3 p0 = ld3<T>(vertices, (size_t)(v0 + i0)), p1 = ld3<T>(vertices, (size_t)(v0 + i1)),
              p2 = ld3<T>(vertices, (size_t)(v0 + i2));
-    const D3 u = sub(p1, p0), v = sub(p2, p0);
-    const D3 n = {u.y * v.z - u.z * v.y, u.z * v.x - u.x * v.z, u.x * v.y - u.y * v.x};
-    const double L = sqrt(dot(n, n));
-    if (L == 0.0 || !finite_f64(L)) continue;
-    const double w = 0.5 * L;
-    const D3 m = {n.x / L, n.y / L, n.z / L};
+    const auto [m, w, usable] = face_plane(p0, p1, p2);
+    if (!usable) continue;
     const double d = -dot(m, sub(p0, g));
     const double wx = w * m.x, wy = w * m.y, wz = w * m.z, wd = -(w * d);
     acc[0] = acc[0] + wx * m.x;
@@ -189,12 +163,8 @@ __global__ __launch_bounds__(DEC_THREADS) void cell_solve_kernel(
     const double l = regularise * W;
     const double axx = acc[0] + l, axy = acc[1], axz = acc[2], ayy = acc[3] + l, ayz = acc[4], azz = acc[5] + l;
     const double bx = acc[6] + l * (acc[10] / W), by = acc[7] + l * (acc[11] / W), bz = acc[8] + l * (acc[12] / W);
-    const double c00 = ayy * azz - ayz * ayz, c01 = axz * ayz - axy * azz, c02 = axy * ayz - axz * ayy;
-    const double c11 = axx * azz - axz * axz, c12 = axy * axz - axx * ayz, c22 = axx * ayy - axy * axy;
-    const double det = (axx * c00 + axy * c01) + axz * c02;
-    y[0] = ((c00 * bx + c01 * by) + c02 * bz) / det;
-    y[1] = ((c01 * bx + c11 * by) + c12 * bz) / det;
-    y[2] = ((c02 * bx + c12 * by) + c22 * bz) / det;
+    const D3 s = solve(adjugate(axx, axy, axz, ayy, ayz, azz), bx, by, bz);
+    y[0] = s.x, y[1] = s.y, y[2] = s.z;
   }
   const double half = 0.5 * hk;
   const double centre[3] = {g.x, g.y, g.z};
@@ -205,22 +175,6 @@ __global__ __launch_bounds__(DEC_THREADS) void cell_solve_kernel(
     out[3 * (long)row + a] = (float)(centre[a] + ya);
   }
 }
-
-// rule 5: one thread per face
-__global__ __launch_bounds__(DEC_THREADS) void compact_faces_kernel(int F, int K, const int *__restrict__ tend,
-                                                                    const int *__restrict__ fcell,
-                                                                    const unsigned char *__restrict__ keep,
-                                                                    const int *__restrict__ fincl,
-                                                                    const int *__restrict__ vincl,
-                                                                    const int *__restrict__ vend2, int *__restrict__ f2) {
-  const long f = (long)blockIdx.x * DEC_THREADS + threadIdx.x;
-  if (f >= F || !keep[f]) return;
-  const int k = segment_of(tend, K, (int)f);
-  const long at = fincl[f] - 1;                        // >= 0: keep[f] is counted in fincl[f]
-  for (int c = 0; c < 3; ++c) f2[3 * at + c] = (vincl[fcell[3 * f + c]] - 1) - vend2[k];     // a kept face's cells are 0..C-1
-}
-
-unsigned blocks_of(long n, int per) { return (unsigned)((n + per - 1) / per); }
 
 int check_batch(int n, int K, int cells) {
   if (n <= 0 || K <= 0) return rfd_invalid("decimate: counts must be positive");
@@ -234,7 +188,7 @@ int check_batch(int n, int K, int cells) {
 RFD_API int rfd_decimate_vertex_keys(int V, int K, int cells, int v_is_f32, const void *vertices, const int *vend,
                                      const double *lo, const double *inv_h, int *key, void *stream) {
   if (int rc = check_batch(V, K, cells)) return rc;
-  if (!vertices || !vend || !lo || !inv_h || !key) return rfd_invalid("rfd_decimate_vertex_keys: a null argument");
+  if (!vertices || !vend || !lo || !inv_h || !key) return MESH_NULL("rfd_decimate_vertex_keys");
   if (v_is_f32)
     vertex_keys_kernel<float><<<blocks_of(V, DEC_THREADS), DEC_THREADS, 0, (hipStream_t)stream>>>(
         V, K, cells, vertices, vend, lo, inv_h, key);
@@ -250,7 +204,7 @@ RFD_API int rfd_decimate_face_remap(int F, int K, int C, const int *faces, const
                                     void *stream) {
   if (F <= 0 || K <= 0 || C <= 0) return rfd_invalid("rfd_decimate_face_remap: counts must be positive");
   if (!faces || !tend || !vend || !vcell || !fcell || !pair || !top || !alive)
-    return rfd_invalid("rfd_decimate_face_remap: a null argument");
+    return MESH_NULL("rfd_decimate_face_remap");
   face_remap_kernel<<<blocks_of(F, DEC_THREADS), DEC_THREADS, 0, (hipStream_t)stream>>>(F, K, C, faces, tend, vend, vcell,
                                                                                         fcell, pair, top, alive);
   RFD_CHECK_LAUNCH();
@@ -260,7 +214,7 @@ RFD_API int rfd_decimate_face_remap(int F, int K, int C, const int *faces, const
 RFD_API int rfd_decimate_parity(int n, int C, int F, const long long *s_pair, const int *s_top, const int *s_face,
                                 const int *fcell, unsigned char *keep, int *used, void *stream) {
   if (n <= 0 || C <= 0 || F <= 0) return rfd_invalid("rfd_decimate_parity: counts must be positive");
-  if (!s_pair || !s_top || !s_face || !fcell || !keep || !used) return rfd_invalid("rfd_decimate_parity: a null argument");
+  if (!s_pair || !s_top || !s_face || !fcell || !keep || !used) return MESH_NULL("rfd_decimate_parity");
   parity_kernel<<<blocks_of(n, DEC_THREADS), DEC_THREADS, 0, (hipStream_t)stream>>>(n, C, F, s_pair, s_top, s_face, fcell,
                                                                                     keep, used);
   RFD_CHECK_LAUNCH();
@@ -275,7 +229,7 @@ RFD_API int rfd_decimate_cell_solve(int C, int K, int F, int cells, int v_is_f32
   if (F <= 0 || (long)F * 3 > INT_MAX) return rfd_invalid("rfd_decimate_cell_solve: 0 < 3 F < 2^31");
   if (!(regularise >= 0.0)) return rfd_invalid("rfd_decimate_cell_solve: regularise must be >= 0");
   if (!vertices || !faces || !vend || !cellkey || !rowptr || !col || !dst || !lo || !h || !out)
-    return rfd_invalid("rfd_decimate_cell_solve: a null argument");
+    return MESH_NULL("rfd_decimate_cell_solve");
   const unsigned grid = blocks_of(C, CELLS_PER_BLOCK);
   if (v_is_f32)
     cell_solve_kernel<float><<<grid, DEC_THREADS, 0, (hipStream_t)stream>>>(C, K, F, cells, vertices, faces, vend, cellkey,
@@ -291,9 +245,11 @@ RFD_API int rfd_decimate_compact_faces(int F, int K, const int *tend, const int 
                                        const int *fincl, const int *vincl, const int *vend2, int *f2, void *stream) {
   if (F <= 0 || K <= 0) return rfd_invalid("rfd_decimate_compact_faces: counts must be positive");
   if (!tend || !fcell || !keep || !fincl || !vincl || !vend2 || !f2)
-    return rfd_invalid("rfd_decimate_compact_faces: a null argument");
-  compact_faces_kernel<<<blocks_of(F, DEC_THREADS), DEC_THREADS, 0, (hipStream_t)stream>>>(F, K, tend, fcell, keep, fincl,
-                                                                                           vincl, vend2, f2);
+    return MESH_NULL("rfd_decimate_compact_faces");
+  // rule 5.  The entry has no cell count to check fcell against: what face_remap_kernel left there is -1 .. C - 1, so
+  // the sign is the check that matters
+  compact_faces_kernel<DEC_THREADS><<<blocks_of(F, DEC_THREADS), DEC_THREADS, 0, (hipStream_t)stream>>>(
+      F, K, INT_MAX, fcell, tend, nullptr, nullptr, keep, fincl, vincl, vend2, f2);
   RFD_CHECK_LAUNCH();
   return 0;
 }

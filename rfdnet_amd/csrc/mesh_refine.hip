@@ -18,22 +18,12 @@
 // A mesh is described by offsets: faces fend[k] .. fend[k+1]-1 (indices local to the mesh), vertices vend[k] .. vend[k+1]-1,
 // decoder tiles tprefix[k] .. tprefix[k+1]-1 (128 query slots each; tprefix[k+1] - tprefix[k] >= ceil(faces / 128)).
 // Everything else is fp32, one rounding per written operation (the library is built with -ffp-contract=off).
-#include "common.h"
+#include "mesh_batch.h"
 #include "rfd_occ.h"
 
 namespace {
 
 constexpr float REFINE_EPS = 1e-10f;             // generator.py:267, :276
-
-// the mesh of face f: the last k with fend[k] <= f (empty meshes repeat an offset); 0 <= f < fend[K]
-__device__ __forceinline__ int mesh_of_face(const int *__restrict__ fend, int K, int f) {
-  int lo = 0, hi = K;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (fend[mid] <= f) lo = mid; else hi = mid;
-  }
-  return lo;
-}
 
 struct Face {
   int slot;           // decoder query slot
@@ -45,10 +35,10 @@ struct Face {
 __device__ __forceinline__ Face load_face(int f, int K, const int *__restrict__ faces, const int *__restrict__ fend,
                                           const int *__restrict__ vend, const int *__restrict__ tprefix) {
   Face fc;
-  const int k = mesh_of_face(fend, K, f);
+  const int k = segment_of(fend, K, f);         // the mesh of face f
   const int f0 = fend[k], v0 = vend[k], nv = vend[k + 1] - v0;
   fc.n_faces = fend[k + 1] - f0;
-  const int j = f - f0;                          // >= 0: mesh_of_face chose k with fend[k] <= f
+  const int j = f - f0;                          // >= 0: segment_of chose k with fend[k] <= f
   const int a = faces[(size_t)f * 3], b = faces[(size_t)f * 3 + 1], c = faces[(size_t)f * 3 + 2];
   fc.ok = (unsigned)a < (unsigned)nv && (unsigned)b < (unsigned)nv && (unsigned)c < (unsigned)nv &&
           j < (tprefix[k + 1] - tprefix[k]) * RFD_OCC_TILE;

@@ -7,40 +7,14 @@
 // each on a marching-cubes mesh), gathers their positions and tests every face; these are scattered 8-byte loads with
 // some sixty f64 operations per face, no reuse a tile could hold, and rows too short to share among lanes, so a wave
 // simply keeps 64 independent walks in flight.  Integer atomicMin only (S4's minima).  Every index read from memory is
-// checked against its array before it is used.
-#include <limits.h>
-
-#include "common.h"
+// checked against its array before it is used: a corner row in walk(), the one place that reads one for the checks of
+// S1 and S3.  The mesh of an item, the f64 helpers and S7's kernel are mesh_batch.h's, shared with mesh_decimate.hip.
+#include "mesh_batch.h"
 #include "../../include/rfd_simplify.h"
 
 namespace {
 
 constexpr int SIM_THREADS = 256;
-
-__device__ __forceinline__ int segment_of(const int *__restrict__ off, int K, int i) {
-  int lo = 0, hi = K;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (off[mid] <= i) lo = mid; else hi = mid;
-  }
-  return lo;
-}
-
-__device__ __forceinline__ bool finite_f64(double v) { return (__double2hiint(v) & 0x7ff00000) != 0x7ff00000; }
-
-struct D3 {
-  double x, y, z;
-};
-__device__ __forceinline__ D3 ld3(const double *__restrict__ p, int i) {
-  const double *q = p + (size_t)i * 3;
-  return {q[0], q[1], q[2]};
-}
-__device__ __forceinline__ D3 sub(D3 a, D3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ double dot(D3 a, D3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
-__device__ __forceinline__ D3 cross(D3 u, D3 v) {
-  return {u.y * v.z - u.z * v.y, u.z * v.x - u.x * v.z, u.x * v.y - u.y * v.x};
-}
-__device__ __forceinline__ bool usable_length(double L) { return L != 0.0 && finite_f64(L); }
 
 struct Tri {
   int i[3];
@@ -53,6 +27,29 @@ __device__ __forceinline__ Tri ld_face(const int *__restrict__ face, int f, int 
   return t;
 }
 __device__ __forceinline__ bool holds(Tri t, int v) { return t.i[0] == v || t.i[1] == v || t.i[2] == v; }
+
+// the working mesh: V positions, F working faces and the corner rows of the round (col has 3 F entries)
+struct Star {
+  int V, F;
+  const int *face;
+  const double *pos;
+  const int *rowptr, *col;
+};
+// The alive faces at the corners of vertex v, in ascending order of the row: body(t, s) sees the face and the slot s of
+// the corner in it and answers whether the walk stops there; -> whether it was stopped.  The one place where a corner
+// row is read: the row is clamped to col, the corner checked against 3 F, the face's indices against V (ld_face).
+template <typename Body>
+__device__ __forceinline__ bool walk(const Star &m, int v, Body body) {
+  const int begin = max(m.rowptr[v], 0), end = min(m.rowptr[v + 1], 3 * m.F);
+  for (int at = begin; at < end; ++at) {
+    const int corner = m.col[at];
+    if ((unsigned)corner >= 3u * (unsigned)m.F) continue;
+    const int f = corner / 3;
+    const Tri t = ld_face(m.face, f, m.V);
+    if (t.i[0] >= 0 && body(t, corner - 3 * f)) return true;
+  }
+  return false;
+}
 
 // S0, first half: one thread per vertex and per face
 template <typename T>
@@ -91,18 +88,10 @@ __global__ __launch_bounds__(SIM_THREADS) void quadrics_kernel(int V, int F, con
   double acc[10];
 #pragma unroll
   for (int t = 0; t < 10; ++t) acc[t] = 0.0;
-  const int begin = max(rowptr[v], 0), end = min(rowptr[v + 1], 3 * F);
-  for (int at = begin; at < end; ++at) {
-    const int corner = col[at];
-    if ((unsigned)corner >= 3u * (unsigned)F) continue;
-    const Tri t = ld_face(face, corner / 3, V);
-    if (t.i[0] < 0) continue;
-    const D3 p0 = ld3(pos, t.i[0]), p1 = ld3(pos, t.i[1]), p2 = ld3(pos, t.i[2]);
-    const D3 n = cross(sub(p1, p0), sub(p2, p0));
-    const double L = sqrt(dot(n, n));
-    if (!usable_length(L)) continue;
-    const double w = 0.5 * L;
-    const D3 m = {n.x / L, n.y / L, n.z / L};
+  walk(Star{V, F, face, pos, rowptr, col}, (int)v, [&](Tri t, int) {
+    const D3 p0 = ld3<double>(pos, t.i[0]), p1 = ld3<double>(pos, t.i[1]), p2 = ld3<double>(pos, t.i[2]);
+    const auto [m, w, usable] = face_plane(p0, p1, p2);
+    if (!usable) return false;
     const double d = -dot(m, p0);
     const double gx = w * m.x, gy = w * m.y, gz = w * m.z, e = w * d;
     acc[0] = acc[0] + gx * m.x;
@@ -115,7 +104,8 @@ __global__ __launch_bounds__(SIM_THREADS) void quadrics_kernel(int V, int F, con
     acc[7] = acc[7] + e * m.y;
     acc[8] = acc[8] + e * m.z;
     acc[9] = acc[9] + e * d;
-  }
+    return false;
+  });
 #pragma unroll
   for (int t = 0; t < 10; ++t) Q[10 * v + t] = acc[t];
 }
@@ -170,17 +160,11 @@ __device__ __forceinline__ double quadric_cost(const Quadric &q, D3 p) {
 }
 
 // S3's flip guard for the faces of `moved` that do not hold `other`; true = rejected
-__device__ bool star_flips(int moved, int other, D3 p, int V, int F, const int *__restrict__ face,
-                           const double *__restrict__ pos, const int *__restrict__ rowptr, const int *__restrict__ col) {
-  const D3 o = ld3(pos, moved);
-  const int begin = max(rowptr[moved], 0), end = min(rowptr[moved + 1], 3 * F);
-  for (int at = begin; at < end; ++at) {
-    const int corner = col[at];
-    if ((unsigned)corner >= 3u * (unsigned)F) continue;
-    const int f = corner / 3, s = corner - 3 * f;
-    const Tri t = ld_face(face, f, V);
-    if (t.i[0] < 0 || t.i[s] != moved || holds(t, other)) continue;
-    const D3 q1 = ld3(pos, t.i[(s + 1) % 3]), q2 = ld3(pos, t.i[(s + 2) % 3]);
+__device__ bool star_flips(Star m, int moved, int other, D3 p) {
+  const D3 o = ld3<double>(m.pos, moved);
+  return walk(m, moved, [&](Tri t, int s) {
+    if (t.i[s] != moved || holds(t, other)) return false;
+    const D3 q1 = ld3<double>(m.pos, t.i[(s + 1) % 3]), q2 = ld3<double>(m.pos, t.i[(s + 2) % 3]);
     const D3 k = cross(sub(q1, o), sub(q2, o));
     const double Lk = sqrt(dot(k, k));
     const D3 d1 = sub(q1, p), d2 = sub(q2, p);
@@ -191,55 +175,33 @@ __device__ bool star_flips(int moved, int other, D3 p, int V, int F, const int *
     const D3 n = cross(u1, u2);
     const double Ln = sqrt(dot(n, n));
     if (!usable_length(Ln)) return true;
-    if (usable_length(Lk) && dot(n, k) < 0.2 * (Ln * Lk)) return true;
-  }
-  return false;
+    return usable_length(Lk) && dot(n, k) < 0.2 * (Ln * Lk);
+  });
 }
 
 // does some alive face of v hold w?
-__device__ bool adjacent(int v, int w, int V, int F, const int *__restrict__ face, const int *__restrict__ rowptr,
-                         const int *__restrict__ col) {
-  const int begin = max(rowptr[v], 0), end = min(rowptr[v + 1], 3 * F);
-  for (int at = begin; at < end; ++at) {
-    const int corner = col[at];
-    if ((unsigned)corner >= 3u * (unsigned)F) continue;
-    const Tri t = ld_face(face, corner / 3, V);
-    if (t.i[0] >= 0 && holds(t, v) && holds(t, w)) return true;
-  }
-  return false;
+__device__ bool adjacent(const Star &m, int v, int w) {
+  return walk(m, v, [&](Tri t, int) { return holds(t, v) && holds(t, w); });
 }
 
 // does a face of v without `other` hold both c0 and c1?
-__device__ bool holds_both_apexes(int v, int other, int c0, int c1, int V, int F, const int *__restrict__ face,
-                                  const int *__restrict__ rowptr, const int *__restrict__ col) {
-  const int begin = max(rowptr[v], 0), end = min(rowptr[v + 1], 3 * F);
-  for (int at = begin; at < end; ++at) {
-    const int corner = col[at];
-    if ((unsigned)corner >= 3u * (unsigned)F) continue;
-    const Tri t = ld_face(face, corner / 3, V);
-    if (t.i[0] >= 0 && holds(t, v) && !holds(t, other) && holds(t, c0) && holds(t, c1)) return true;
-  }
-  return false;
+__device__ bool holds_both_apexes(const Star &m, int v, int other, int c0, int c1) {
+  return walk(m, v, [&](Tri t, int) { return holds(t, v) && !holds(t, other) && holds(t, c0) && holds(t, c1); });
 }
 
 // S3's link condition; true = holds
-__device__ bool link_ok(int a, int b, int c0, int c1, int V, int F, const int *__restrict__ face,
-                        const int *__restrict__ rowptr, const int *__restrict__ col) {
+__device__ bool link_ok(Star m, int a, int b, int c0, int c1) {
   if (c0 == c1) return false;
-  const int begin = max(rowptr[a], 0), end = min(rowptr[a + 1], 3 * F);
-  for (int at = begin; at < end; ++at) {
-    const int corner = col[at];
-    if ((unsigned)corner >= 3u * (unsigned)F) continue;
-    const Tri t = ld_face(face, corner / 3, V);
-    if (t.i[0] < 0 || !holds(t, a) || holds(t, b)) continue;
+  const bool pinched = walk(m, a, [&](Tri t, int) {
+    if (!holds(t, a) || holds(t, b)) return false;
     for (int s = 0; s < 3; ++s) {
       const int w = t.i[s];
       if (w == a || w == c0 || w == c1) continue;
-      if (adjacent(b, w, V, F, face, rowptr, col)) return false;
+      if (adjacent(m, b, w)) return true;
     }
-  }
-  return !(holds_both_apexes(a, b, c0, c1, V, F, face, rowptr, col) &&
-           holds_both_apexes(b, a, c0, c1, V, F, face, rowptr, col));
+    return false;
+  });
+  return !pinched && !(holds_both_apexes(m, a, b, c0, c1) && holds_both_apexes(m, b, a, c0, c1));
 }
 
 // S2 and S3: one thread per edge slot
@@ -261,19 +223,13 @@ __global__ __launch_bounds__(SIM_THREADS) void edge_costs_kernel(
     const double *qa = Q + 10 * (size_t)a, *qb = Q + 10 * (size_t)b;
     const Quadric q = {qa[0] + qb[0], qa[1] + qb[1], qa[2] + qb[2], qa[3] + qb[3], qa[4] + qb[4],
                        qa[5] + qb[5], qa[6] + qb[6], qa[7] + qb[7], qa[8] + qb[8], qa[9] + qb[9]};
-    const D3 pa = ld3(pos, a), pb = ld3(pos, b);
+    const D3 pa = ld3<double>(pos, a), pb = ld3<double>(pos, b);
     const D3 mid = {(pa.x + pb.x) * 0.5, (pa.y + pb.y) * 0.5, (pa.z + pb.z) * 0.5};
     const D3 t = sub(pb, pa);
     const double len2 = dot(t, t);
-    const double c00 = q.ayy * q.azz - q.ayz * q.ayz, c01 = q.axz * q.ayz - q.axy * q.azz,
-                 c02 = q.axy * q.ayz - q.axz * q.ayy;
-    const double c11 = q.axx * q.azz - q.axz * q.axz, c12 = q.axy * q.axz - q.axx * q.ayz,
-                 c22 = q.axx * q.ayy - q.axy * q.axy;
-    const double det = (q.axx * c00 + q.axy * c01) + q.axz * c02;
-    if (det != 0.0 && finite_f64(det)) {
-      const double rx = -q.bx, ry = -q.by, rz = -q.bz;
-      const D3 y = {((c00 * rx + c01 * ry) + c02 * rz) / det, ((c01 * rx + c11 * ry) + c12 * rz) / det,
-                    ((c02 * rx + c12 * ry) + c22 * rz) / det};
+    const Adjugate3 adj = adjugate(q.axx, q.axy, q.axz, q.ayy, q.ayz, q.azz);
+    if (adj.det != 0.0 && finite_f64(adj.det)) {
+      const D3 y = solve(adj, -q.bx, -q.by, -q.bz);
       if (finite_f64(y.x) && finite_f64(y.y) && finite_f64(y.z)) {
         const D3 s = sub(y, mid);
         if (dot(s, s) <= len2) {
@@ -288,8 +244,8 @@ __global__ __launch_bounds__(SIM_THREADS) void edge_costs_kernel(
       const double c = quadric_cost(q, rest[j]);
       if (c < best) best = c, p = rest[j];
     }
-    ok = best < inf && link_ok(a, b, c0, c1, V, F, face, rowptr, col) &&
-         !star_flips(a, b, p, V, F, face, pos, rowptr, col) && !star_flips(b, a, p, V, F, face, pos, rowptr, col);
+    const Star m = {V, F, face, pos, rowptr, col};
+    ok = best < inf && link_ok(m, a, b, c0, c1) && !star_flips(m, a, b, p) && !star_flips(m, b, a, p);
   }
   cost[i] = ok ? best + 0.0 : inf;          // -0 + 0 = +0: one zero for the sort
   epos[3 * i] = p.x, epos[3 * i + 1] = p.y, epos[3 * i + 2] = p.z;
@@ -354,31 +310,6 @@ __global__ __launch_bounds__(SIM_THREADS) void apply_kernel(int V, int F, const 
   for (int t = 0; t < 3; ++t) face[3 * (size_t)f0 + t] = -1, face[3 * (size_t)f1 + t] = -1;
 }
 
-// S7: one thread per face
-__global__ __launch_bounds__(SIM_THREADS) void compact_kernel(int V, int F, int K, const int *__restrict__ faces,
-                                                              const int *__restrict__ face, const int *__restrict__ vend,
-                                                              const int *__restrict__ tend,
-                                                              const unsigned char *__restrict__ takes_part,
-                                                              const unsigned char *__restrict__ keep,
-                                                              const int *__restrict__ fincl, const int *__restrict__ vincl,
-                                                              const int *__restrict__ vend2, int *__restrict__ f2) {
-  const long f = (long)blockIdx.x * SIM_THREADS + threadIdx.x;
-  if (f >= F || !keep[f]) return;
-  const int k = segment_of(tend, K, (int)f);
-  const long at = fincl[f] - 1;                        // >= 0: keep[f] is counted in fincl[f]
-  if (at < 0 || at >= F) return;
-  for (int c = 0; c < 3; ++c) {
-    int out = faces[3 * f + c];                        // a mesh that takes no part: as it went in
-    if (takes_part[k]) {
-      const int g = face[3 * f + c];
-      out = (unsigned)g < (unsigned)V ? (vincl[g] - 1) - vend2[k] : -1;
-    }
-    f2[3 * at + c] = out;
-  }
-}
-
-unsigned blocks_of(long n) { return (unsigned)((n + SIM_THREADS - 1) / SIM_THREADS); }
-
 int check_sizes(const char *msg, int V, int F) {
   if (V <= 0 || F <= 0 || (long)F * 3 > INT_MAX) return rfd_invalid(msg);
   return 0;
@@ -386,15 +317,14 @@ int check_sizes(const char *msg, int V, int F) {
 
 }  // namespace
 
-#define SIM_NULL(who) rfd_invalid(who ": a null argument")
-
 RFD_API int rfd_simplify_init(int V, int F, int K, int v_is_f32, const void *vertices, const int *faces, const int *vend,
                               const int *tend, const int *n_faces, double *pos, unsigned char *nonfinite, int *face,
                               void *stream) {
   if (int rc = check_sizes("rfd_simplify_init: V > 0 and 0 < 3 F < 2^31", V, F)) return rc;
   if (K <= 0) return rfd_invalid("rfd_simplify_init: K must be positive");
-  if (!vertices || !faces || !vend || !tend || !n_faces || !pos || !nonfinite || !face) return SIM_NULL("rfd_simplify_init");
-  const unsigned grid = blocks_of(V > F ? V : F);
+  if (!vertices || !faces || !vend || !tend || !n_faces || !pos || !nonfinite || !face)
+    return MESH_NULL("rfd_simplify_init");
+  const unsigned grid = blocks_of(V > F ? V : F, SIM_THREADS);
   if (v_is_f32)
     init_kernel<float><<<grid, SIM_THREADS, 0, (hipStream_t)stream>>>(V, F, K, vertices, faces, vend, tend, n_faces, pos,
                                                                       nonfinite, face);
@@ -408,8 +338,8 @@ RFD_API int rfd_simplify_init(int V, int F, int K, int v_is_f32, const void *ver
 RFD_API int rfd_simplify_quadrics(int V, int F, const double *pos, const int *face, const int *rowptr, const int *col,
                                   double *Q, void *stream) {
   if (int rc = check_sizes("rfd_simplify_quadrics: V > 0 and 0 < 3 F < 2^31", V, F)) return rc;
-  if (!pos || !face || !rowptr || !col || !Q) return SIM_NULL("rfd_simplify_quadrics");
-  quadrics_kernel<<<blocks_of(V), SIM_THREADS, 0, (hipStream_t)stream>>>(V, F, pos, face, rowptr, col, Q);
+  if (!pos || !face || !rowptr || !col || !Q) return MESH_NULL("rfd_simplify_quadrics");
+  quadrics_kernel<<<blocks_of(V, SIM_THREADS), SIM_THREADS, 0, (hipStream_t)stream>>>(V, F, pos, face, rowptr, col, Q);
   RFD_CHECK_LAUNCH();
   return 0;
 }
@@ -418,9 +348,9 @@ RFD_API int rfd_simplify_edges(int V, int F, const long long *skey, const int *h
                                int *eface, int *eapex, unsigned char *efrozen, unsigned char *vfrozen, void *stream) {
   if (int rc = check_sizes("rfd_simplify_edges: V > 0 and 0 < 3 F < 2^31", V, F)) return rc;
   if (!skey || !horder || !face || !ea || !eb || !eface || !eapex || !efrozen || !vfrozen)
-    return SIM_NULL("rfd_simplify_edges");
-  edges_kernel<<<blocks_of(3l * F), SIM_THREADS, 0, (hipStream_t)stream>>>(V, F, skey, horder, face, ea, eb, eface, eapex,
-                                                                          efrozen, vfrozen);
+    return MESH_NULL("rfd_simplify_edges");
+  edges_kernel<<<blocks_of(3l * F, SIM_THREADS), SIM_THREADS, 0, (hipStream_t)stream>>>(V, F, skey, horder, face, ea, eb,
+                                                                                        eface, eapex, efrozen, vfrozen);
   RFD_CHECK_LAUNCH();
   return 0;
 }
@@ -433,8 +363,8 @@ RFD_API int rfd_simplify_edge_costs(int V, int F, int K, const int *vend, const 
   if (K <= 0) return rfd_invalid("rfd_simplify_edge_costs: K must be positive");
   if (!vend || !ea || !eb || !eapex || !efrozen || !vfrozen || !face || !pos || !Q || !rowptr || !col || !cost || !epos ||
       !legal || !emesh)
-    return SIM_NULL("rfd_simplify_edge_costs");
-  edge_costs_kernel<<<blocks_of(3l * F), SIM_THREADS, 0, (hipStream_t)stream>>>(
+    return MESH_NULL("rfd_simplify_edge_costs");
+  edge_costs_kernel<<<blocks_of(3l * F, SIM_THREADS), SIM_THREADS, 0, (hipStream_t)stream>>>(
       V, F, K, vend, ea, eb, eapex, efrozen, vfrozen, face, pos, Q, rowptr, col, cost, epos, legal, emesh);
   RFD_CHECK_LAUNCH();
   return 0;
@@ -445,8 +375,9 @@ RFD_API int rfd_simplify_vertex_min(int V, int F, int pass, const int *ea, const
   if (int rc = check_sizes("rfd_simplify_vertex_min: V > 0 and 0 < 3 F < 2^31", V, F)) return rc;
   if (pass != 0 && pass != 1) return rfd_invalid("rfd_simplify_vertex_min: pass is 0 or 1");
   if (!ea || !eb || !vmin || (pass == 0 && (!legal || !rank)) || (pass == 1 && !other))
-    return SIM_NULL("rfd_simplify_vertex_min");
-  vertex_min_kernel<<<blocks_of(3l * F), SIM_THREADS, 0, (hipStream_t)stream>>>(V, F, pass, ea, eb, legal, rank, other, vmin);
+    return MESH_NULL("rfd_simplify_vertex_min");
+  vertex_min_kernel<<<blocks_of(3l * F, SIM_THREADS), SIM_THREADS, 0, (hipStream_t)stream>>>(V, F, pass, ea, eb, legal,
+                                                                                             rank, other, vmin);
   RFD_CHECK_LAUNCH();
   return 0;
 }
@@ -454,8 +385,9 @@ RFD_API int rfd_simplify_vertex_min(int V, int F, int pass, const int *ea, const
 RFD_API int rfd_simplify_select(int V, int F, const int *ea, const int *eb, const unsigned char *legal, const int *rank,
                                 const int *m2, unsigned char *sel, void *stream) {
   if (int rc = check_sizes("rfd_simplify_select: V > 0 and 0 < 3 F < 2^31", V, F)) return rc;
-  if (!ea || !eb || !legal || !rank || !m2 || !sel) return SIM_NULL("rfd_simplify_select");
-  select_kernel<<<blocks_of(3l * F), SIM_THREADS, 0, (hipStream_t)stream>>>(V, F, ea, eb, legal, rank, m2, sel);
+  if (!ea || !eb || !legal || !rank || !m2 || !sel) return MESH_NULL("rfd_simplify_select");
+  select_kernel<<<blocks_of(3l * F, SIM_THREADS), SIM_THREADS, 0, (hipStream_t)stream>>>(V, F, ea, eb, legal, rank, m2,
+                                                                                         sel);
   RFD_CHECK_LAUNCH();
   return 0;
 }
@@ -464,9 +396,9 @@ RFD_API int rfd_simplify_apply(int V, int F, const unsigned char *keep, const in
                                const double *epos, const int *rowptr, const int *col, double *pos, double *Q, int *face,
                                void *stream) {
   if (int rc = check_sizes("rfd_simplify_apply: V > 0 and 0 < 3 F < 2^31", V, F)) return rc;
-  if (!keep || !ea || !eb || !eface || !epos || !rowptr || !col || !pos || !Q || !face) return SIM_NULL("rfd_simplify_apply");
-  apply_kernel<<<blocks_of(3l * F), SIM_THREADS, 0, (hipStream_t)stream>>>(V, F, keep, ea, eb, eface, epos, rowptr, col, pos,
-                                                                          Q, face);
+  if (!keep || !ea || !eb || !eface || !epos || !rowptr || !col || !pos || !Q || !face) return MESH_NULL("rfd_simplify_apply");
+  apply_kernel<<<blocks_of(3l * F, SIM_THREADS), SIM_THREADS, 0, (hipStream_t)stream>>>(V, F, keep, ea, eb, eface, epos,
+                                                                                        rowptr, col, pos, Q, face);
   RFD_CHECK_LAUNCH();
   return 0;
 }
@@ -477,9 +409,9 @@ RFD_API int rfd_simplify_compact_faces(int V, int F, int K, const int *faces, co
   if (int rc = check_sizes("rfd_simplify_compact_faces: V > 0 and 0 < 3 F < 2^31", V, F)) return rc;
   if (K <= 0) return rfd_invalid("rfd_simplify_compact_faces: K must be positive");
   if (!faces || !face || !vend || !tend || !takes_part || !keep || !fincl || !vincl || !vend2 || !f2)
-    return SIM_NULL("rfd_simplify_compact_faces");
-  compact_kernel<<<blocks_of(F), SIM_THREADS, 0, (hipStream_t)stream>>>(V, F, K, faces, face, vend, tend, takes_part, keep,
-                                                                        fincl, vincl, vend2, f2);
+    return MESH_NULL("rfd_simplify_compact_faces");
+  compact_faces_kernel<SIM_THREADS><<<blocks_of(F, SIM_THREADS), SIM_THREADS, 0, (hipStream_t)stream>>>(
+      F, K, V, face, tend, takes_part, faces, keep, fincl, vincl, vend2, f2);                       // S7
   RFD_CHECK_LAUNCH();
   return 0;
 }

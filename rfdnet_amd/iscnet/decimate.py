@@ -11,7 +11,7 @@ Deterministic: stable sorts and prefix sums between the kernels, fixed-shape sum
 import numpy as np
 import torch
 
-from .. import _lib, ragged
+from .. import _lib, mesh_batch, ragged
 
 PADDING = 0.1           # Generator3D's default: the default cube is [-(1 + PADDING) / 2, (1 + PADDING) / 2]^3
 REGULARISE = 1e-3       # a choice, not a tuned value: pulls a badly conditioned quadric solve towards the weighted mean
@@ -23,14 +23,6 @@ def default_cube(K, cells, padding=PADDING):
     return np.full((K, 3), -box / 2, dtype=np.float64), np.full(K, box / cells, dtype=np.float64)
 
 
-def _offsets(end, what):
-    end = np.asarray([int(x) for x in end], dtype=np.int64)
-    if end.ndim != 1 or end.size < 1 or end[0] != 0 or (np.diff(end) < 0).any():
-        raise ValueError("%s: K + 1 ascending offsets starting at 0" % what)
-    ragged.offsets(np.diff(end))            # the total stays below 2^31
-    return end
-
-
 @torch.no_grad()
 def decimate_meshes(v, f, vend, tend, cells, lo=None, h=None, regularise=REGULARISE):
     """v (V,3) f64 / f32 vertices, f (F,3) i32 faces with indices local to their mesh, vend / tend the K + 1 vertex / face
@@ -38,18 +30,13 @@ def decimate_meshes(v, f, vend, tend, cells, lo=None, h=None, regularise=REGULAR
     every mesh (default: default_cube()), regularise: see REGULARISE
     -> (v2 (V2,3) f32, f2 (F2,3) i32, vend2, tend2): the decimated batch in the same layout; the offsets (Python lists)
     come back through one small D2H copy.  ValueError for cells < 1 or K cells^3 >= 2^31, before anything is allocated."""
-    vend, tend = _offsets(vend, "vend"), _offsets(tend, "tend")
-    K = len(vend) - 1
+    vend, tend, K = mesh_batch.check_offsets(vend, tend)
     cells = int(cells)
-    if len(tend) != K + 1:
-        raise ValueError("vend and tend describe %d and %d meshes" % (K, len(tend) - 1))
     if cells < 1:
         raise ValueError("cells must be >= 1, not %d" % cells)
     if K * cells ** 3 >= ragged.INT32_END:
         raise ValueError("%d meshes of %d^3 cells: the keys must stay below 2^31 (int32)" % (K, cells))
-    _lib.need_gpu(v, f)
-    if v.dtype not in (torch.float64, torch.float32):
-        raise TypeError("vertices must be float64 or float32, not %s" % v.dtype)
+    mesh_batch.check_tensors(v, f)
     if lo is None or h is None:
         dlo, dh = default_cube(K, cells)
         lo, h = dlo if lo is None else lo, dh if h is None else h
@@ -113,19 +100,15 @@ def decimate_meshes(v, f, vend, tend, cells, lo=None, h=None, regularise=REGULAR
               fcell.data_ptr(), keep.data_ptr(), used.data_ptr())
 
     # rule 5: the new offsets (the one D2H copy), then positions of the used cells and the kept faces
-    vincl = torch.cumsum(used, 0, dtype=torch.int32)
-    fincl = torch.cumsum(keep, 0, dtype=torch.int32)
-    zero = torch.zeros(1, dtype=torch.int32, device=dev)
     first_cell = torch.searchsorted(cellkey, torch.arange(K + 1, dtype=torch.int64, device=dev).mul_(per).int())
-    bounds = torch.stack([torch.cat([zero, vincl])[first_cell], torch.cat([zero, fincl])[tend_d.long()]])
+    vincl, fincl, bounds = mesh_batch.compacted_offsets(used, keep, first_cell, tend_d.long())
     vend2, tend2 = bounds.cpu().tolist()
     V2, F2 = vend2[-1], tend2[-1]
     if F2 == 0:
         return empty()
     v2 = torch.empty(V2, 3, dtype=torch.float32, device=dev)
     f2 = torch.empty(F2, 3, dtype=torch.int32, device=dev)
-    from .generator import vertex_corner_csr
-    rowptr, col = vertex_corner_csr(fcell, C)                               # cell -> corners 3 face + c, ascending
+    rowptr, col = mesh_batch.corner_csr(fcell, C)                           # cell -> corners 3 face + c, ascending
     dst = torch.where(used > 0, vincl - 1, torch.full_like(vincl, -1))
     _lib.call("rfd_decimate_cell_solve", dev, C, K, F, cells, is_f32, vv.data_ptr(), ff.data_ptr(), vend_d.data_ptr(),
               cellkey.data_ptr(), rowptr.data_ptr(), col.data_ptr(), dst.data_ptr(), lo_d.data_ptr(), h_d.data_ptr(),

@@ -17,7 +17,7 @@ import os
 import numpy as np
 import torch
 
-from .. import _lib, ragged
+from .. import _lib, mesh_batch, ragged
 from .occ_decoder import GROUP, MODE_F16X3, TILE, logit_threshold, run_with_range_fallback
 
 
@@ -44,19 +44,6 @@ def draw_dirichlet(face_counts, steps):
                 out[it, at:at + n] = np.random.dirichlet((0.5, 0.5, 0.5), size=n)
         at += n
     return out
-
-
-def vertex_corner_csr(faces, n_vertices):
-    """faces (F,3) integer tensor of GLOBAL vertex indices -> (rowptr (n_vertices + 1,) i32, col (3F,) i32): the corners
-    3 f + c of vertex v are col[rowptr[v]:rowptr[v+1]], ascending (a stable sort of the flattened faces).  A vertex no face
-    names has an empty row; an index outside [0, n_vertices) is in no row."""
-    flat = faces.reshape(-1).long()
-    assert flat.numel() < 2 ** 31
-    flat = torch.where((flat >= 0) & (flat < n_vertices), flat, torch.full_like(flat, n_vertices))
-    col = torch.sort(flat, stable=True).indices
-    rowptr = torch.zeros(n_vertices + 1, dtype=torch.int64, device=faces.device)
-    rowptr[1:] = torch.cumsum(torch.bincount(flat, minlength=n_vertices + 1)[:n_vertices], 0)
-    return rowptr.int(), col.int()
 
 
 class Generator3D(object):
@@ -365,7 +352,7 @@ class Generator3D(object):
             tile_prop = ragged.to_int32(tiles.owner, dev)
             faces = f[:F].to(torch.int32).contiguous()
             first = torch.repeat_interleave(vend_d[:-1].long(), torch.as_tensor(counts, device=dev), output_size=F)
-            rowptr, col = vertex_corner_csr(faces.long() + first[:, None], V)
+            rowptr, col = mesh_batch.corner_csr(faces.long() + first[:, None], V)
             if eps is not None:
                 eps = torch.as_tensor(np.ascontiguousarray(eps, dtype=np.float32)) if not torch.is_tensor(eps) else eps
                 assert tuple(eps.shape) == (steps, F, 3)

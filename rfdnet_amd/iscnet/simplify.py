@@ -11,8 +11,7 @@ prefix sums between the kernels, integer minima inside them."""
 import numpy as np
 import torch
 
-from .. import _lib, ragged
-from .decimate import _offsets
+from .. import _lib, mesh_batch, ragged
 
 MAX_ROUNDS = 1000       # a bound, not a tuned value: a round removes a few per cent of the faces, or nothing (then it stops)
 INT32_MAX = 2 ** 31 - 1
@@ -30,15 +29,6 @@ def _targets(n_faces, K):
     return np.minimum(n, INT32_MAX)
 
 
-def _corner_csr(face, V):
-    """generator.vertex_corner_csr for the working faces (-1 -1 -1 = dead), without a host synchronisation"""
-    flat = face.reshape(-1).long()
-    flat = torch.where(flat >= 0, flat, torch.full_like(flat, V))
-    skey, col = torch.sort(flat, stable=True)
-    rowptr = torch.searchsorted(skey, torch.arange(V + 1, dtype=torch.int64, device=face.device))
-    return rowptr.int(), col.int()
-
-
 @torch.no_grad()
 def simplify_meshes(v, f, vend, tend, n_faces, max_rounds=MAX_ROUNDS, stats=None):
     """v (V,3) f64 / f32 vertices, f (F,3) i32 faces with indices local to their mesh, vend / tend the K + 1 vertex / face
@@ -48,17 +38,12 @@ def simplify_meshes(v, f, vend, tend, n_faces, max_rounds=MAX_ROUNDS, stats=None
     down to its target (a mesh of frozen vertices, or one whose every collapse would pinch or flip, cannot).  One small
     D2H copy per round.  stats: a dict that receives 'rounds', 'launches' (of this module's kernels) and 'host_syncs'.
     ValueError / TypeError for bad offsets or targets before anything is allocated."""
-    vend, tend = _offsets(vend, "vend"), _offsets(tend, "tend")
-    K = len(vend) - 1
-    if len(tend) != K + 1:
-        raise ValueError("vend and tend describe %d and %d meshes" % (K, len(tend) - 1))
+    vend, tend, K = mesh_batch.check_offsets(vend, tend)
     n_faces = _targets(n_faces, K)
     max_rounds = int(max_rounds)
     if max_rounds < 0:
         raise ValueError("max_rounds must be >= 0")
-    _lib.need_gpu(v, f)
-    if v.dtype not in (torch.float64, torch.float32):
-        raise TypeError("vertices must be float64 or float32, not %s" % v.dtype)
+    mesh_batch.check_tensors(v, f)
     dev = v.device
     V, F = int(vend[-1]), int(tend[-1])
     assert v.shape[0] >= V and f.shape[0] >= F
@@ -85,7 +70,7 @@ def simplify_meshes(v, f, vend, tend, n_faces, max_rounds=MAX_ROUNDS, stats=None
     face = torch.empty(F, 3, dtype=torch.int32, device=dev)
     call("rfd_simplify_init", V1, F, K, is_f32, vv.data_ptr(), ff.data_ptr(), vend_d.data_ptr(), tend_d.data_ptr(),
          nf_d.data_ptr(), pos.data_ptr(), nonfinite.data_ptr(), face.data_ptr())
-    rowptr, col = _corner_csr(face, V1)
+    rowptr, col = mesh_batch.corner_csr(face, V1)                           # dead faces (-1 -1 -1) are in no row
     Q = torch.empty(V1, 10, dtype=torch.float64, device=dev)
     call("rfd_simplify_quadrics", V1, F, pos.data_ptr(), face.data_ptr(), rowptr.data_ptr(), col.data_ptr(), Q.data_ptr())
 
@@ -111,7 +96,7 @@ def simplify_meshes(v, f, vend, tend, n_faces, max_rounds=MAX_ROUNDS, stats=None
     while pending > 0 and count['rounds'] < max_rounds:
         count['rounds'] += 1
         if count['rounds'] > 1:
-            rowptr, col = _corner_csr(face, V1)
+            rowptr, col = mesh_batch.corner_csr(face, V1)
         # S0: the half-edges 3 face + c (corner c to the next) grouped by edge, dead ones last
         a, b = face.reshape(-1).long(), face[:, [1, 2, 0]].reshape(-1).long()
         key = torch.where(a >= 0, torch.minimum(a, b) * V1 + torch.maximum(a, b), torch.full_like(a, V1 * V1))
@@ -161,10 +146,7 @@ def simplify_meshes(v, f, vend, tend, n_faces, max_rounds=MAX_ROUNDS, stats=None
     used = used[:V1] | ~part_v
     if V == 0:
         used[:] = False
-    vincl = torch.cumsum(used, 0, dtype=torch.int32)
-    fincl = torch.cumsum(keep_f, 0, dtype=torch.int32)
-    zero32 = zero.int()
-    bounds = torch.stack([torch.cat([zero32, vincl])[vend_d.long()], torch.cat([zero32, fincl])[tend_l]])
+    vincl, fincl, bounds = mesh_batch.compacted_offsets(used, keep_f, vend_d.long(), tend_l)
     vend2, tend2, alive_h = torch.cat([bounds, torch.cat([alive_k, zero]).int()[None]]).cpu().tolist()
     count['host_syncs'] += 1
     v2 = pos[used]

@@ -188,6 +188,32 @@ def test_a_mesh_alone_equals_itself_in_a_batch_and_two_calls_are_equal(hip):
     assert np.array_equal(one[0][first].view(np.uint32), one[0][last].view(np.uint32))
 
 
+def test_empty_meshes_at_the_head_and_twice_in_a_row(hip):
+    """[empty, tetrahedron, empty, empty, octahedron]: offsets that begin with a repeat and repeat twice in the middle, the
+    inputs of the search for the mesh of a vertex or face.  Two cells a side; every vertex of both meshes has a cell of
+    its own, so every face stays.  (An octahedron with its vertices ON the axes cannot do that in any 2^3 grid -- one vertex
+    of every axis shares the cell of the origin -- so this one has them pushed into six octants.)"""
+    tet = (np.array([[0., 0., 0.], [1., 0., 0.], [0., 1., 0.], [0., 0., 1.]]),
+           np.array([[0, 2, 1], [0, 1, 3], [1, 2, 3], [0, 3, 2]]))
+    octa = (np.array([[1., .2, .2], [-1., -.2, -.2], [-.2, 1.25, .2], [.2, -1., -.2], [.2, -.2, 1.5], [-.2, .2, -.75]]),
+            np.array([[0, 2, 4], [2, 1, 4], [1, 3, 4], [3, 0, 4], [2, 0, 5], [1, 2, 5], [3, 1, 5], [0, 3, 5]]))
+    meshes = [EMPTY, tet, EMPTY, EMPTY, octa]
+    v, f, vend, tend = cases.batch(meshes)
+    lo = np.array([[0.] * 3, [-.5] * 3, [0.] * 3, [0.] * 3, [-2.] * 3])
+    h = np.array([1., 1., 1., 1., 2.])
+    for k in (1, 4):
+        ijk, has = D.vertex_cells(meshes[k][0], lo[k], h[k], 2)
+        assert has.all() and len(set(map(tuple, ijk.tolist()))) == len(meshes[k][0])
+    got, want = both("empties around a tetrahedron and an octahedron", v, f, vend, tend, 2, lo, h)
+    hip.device_status()
+    assert got[2] == [0, 0, 4, 4, 4, 10] and got[3] == [0, 0, 4, 4, 4, 12]
+    for k in (1, 4):
+        mv, mf = meshes[k]
+        alone = on_device(mv, mf, [0, len(mv)], [0, len(mf)], 2, lo=lo[k:k + 1], h=h[k:k + 1])
+        vs, fs = slice(got[2][k], got[2][k + 1]), slice(got[3][k], got[3][k + 1])
+        assert np.array_equal(got[0][vs].view(np.uint32), alone[0].view(np.uint32)) and np.array_equal(got[1][fs], alone[1])
+
+
 # 8 -------------------------------------------------------------------------------------------------------------------
 def test_a_thin_sheet_loses_its_duplicates_mod_2(hip):
     v, f = cases.slab()

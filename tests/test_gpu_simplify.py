@@ -89,6 +89,22 @@ def test_a_mesh_alone_equals_itself_in_the_batch_and_two_calls_are_equal(hip, wh
     assert again[2:4] == got[2:4] and np.array_equal(again[4], got[4])
 
 
+def test_empty_meshes_at_the_head_and_twice_in_a_row(hip):
+    """[empty, tetrahedron, empty, empty, octahedron] to six faces: offsets that begin with a repeat and repeat twice in the
+    middle, the inputs of the search for the mesh of a vertex or face.  Only the octahedron takes part."""
+    meshes = [C.EMPTY, C.tetrahedron(), C.EMPTY, C.EMPTY, C.octahedron()]
+    v, f, vend, tend = C.batch(meshes)
+    got = on_device(v, f, vend, tend, 6)
+    hip.device_status()
+    assert_mesh("octahedron behind empties", got, 4, C.restated('octahedron')[0])
+    assert got[3][5] - got[3][4] == 6
+    for k in range(4):                                                  # as they went in
+        mv, mf = meshes[k]
+        assert_mesh("mesh %d" % k, got, k, S.simplify(mv, mf, 6))
+        vs, fs = slice(got[2][k], got[2][k + 1]), slice(got[3][k], got[3][k + 1])
+        assert np.array_equal(bits(got[0][vs]), bits(mv)) and np.array_equal(got[1][fs], mf) and got[4][k]
+
+
 # 5 -------------------------------------------------------------------------------------------------------------------
 def test_targets_from_one_collapse_to_none(hip):
     (v, f), _ = C.CASES['icosphere320']

@@ -1,6 +1,6 @@
 """CPU: mesh refinement (Generator3D.set_refinement / refine_meshes, csrc/mesh_refine.hip) -- the float64 closed-form
 restatement (tests/refine_f64.py) against the fixture of the reference's refine_mesh (F_REF: its double-backward float64 run),
-the host draw order, the vertex -> corner CSR, configuration and binding.  No kernel runs here."""
+the host draw order, configuration and binding.  No kernel runs here."""
 import os
 import re
 import sys
@@ -61,25 +61,6 @@ def test_host_draw_consumes_numpys_stream_in_the_references_order(fx):
         a = refine_f64(sd, ref["verts"], faces[k], z, code, batched[:, lo:hi], tau)
         b = refine_f64(sd, ref["verts"], faces[k], z, code, sequential[k], tau)
         assert np.array_equal(a, b) and np.abs(a - ref["verts"]).max() > 1e-4
-
-
-def test_vertex_corner_csr():
-    from rfdnet_amd.iscnet.generator import vertex_corner_csr
-    # vertex 2 twice in face 1, vertex 4 unreferenced, vertex 5 only in the last face
-    faces = torch.tensor([[0, 1, 2], [2, 3, 2], [1, 0, 3], [5, 0, 1]])
-    rowptr, col = vertex_corner_csr(faces, 6)
-    assert rowptr.dtype == torch.int32 and col.dtype == torch.int32
-    assert rowptr.tolist() == [0, 3, 6, 9, 11, 11, 12]
-    rows = [col[rowptr[v]:rowptr[v + 1]].tolist() for v in range(6)]
-    assert rows == [[0, 7, 10], [1, 6, 11], [2, 3, 5], [4, 8], [], [9]]          # ascending (face, corner)
-    flat = faces.reshape(-1)
-    assert all(int(flat[c]) == v for v in range(6) for c in rows[v])
-    # an empty mesh in the middle of a batch is an empty range of both buffers; no faces at all: empty rows
-    rowptr, col = vertex_corner_csr(torch.zeros(0, 3, dtype=torch.int64), 4)
-    assert rowptr.tolist() == [0, 0, 0, 0, 0] and col.numel() == 0
-    # an index outside the vertex range is in no row
-    rowptr, col = vertex_corner_csr(torch.tensor([[0, 9, 1], [1, -1, 0]]), 2)
-    assert rowptr.tolist() == [0, 2, 4] and col[:4].tolist() == [0, 5, 2, 3]
 
 
 def test_config_enables_refinement_and_the_constructor_still_raises():
