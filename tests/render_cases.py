@@ -15,6 +15,11 @@ import torch
 import render_f64
 
 NEAR = 0.25
+# The two constants of rfdnet_amd/csrc/raster.hip (raster_triangles_kernel) that the cases from 7 on are aimed at:
+# primitive p is thread p % RASTER_THREADS of workgroup p // RASTER_THREADS, and a triangle whose clamped pixel box has
+# more than SMALL_BOX pixels is not walked by its own thread but by all the threads of its workgroup together.
+SMALL_BOX = 64
+RASTER_THREADS = 256
 
 
 def camera(width, height, focal=None):
@@ -51,6 +56,19 @@ def shared_edge_pixels(on_centres):
     return 11 * 11 if on_centres else 12 * 12
 
 
+def shared_edge_small(on_centres):
+    """shared_edge() shrunk until each half is walked by its own thread: 2.5 .. 9.5 (rows and columns 2..8 are covered,
+    9 is not) or 2 .. 10; either way both triangles have a box of exactly 8 x 8 = SMALL_BOX pixels"""
+    cam = camera(16, 16)
+    lo, hi = (2.5, 9.5) if on_centres else (2., 10.)
+    v = [at(cam, lo, lo, 2.), at(cam, hi, lo, 2.), at(cam, hi, hi, 2.), at(cam, lo, hi, 2.)]
+    return case(cam, v, [[0, 1, 2], [0, 2, 3]])
+
+
+def shared_edge_small_pixels(on_centres):
+    return 7 * 7 if on_centres else 8 * 8
+
+
 # 2 --------------------------------------------------------------------------------------------------- the depth test ----
 def overlap(order=(0, 1, 2), duplicate=False):
     """two tilted triangles that cross over each other's depth range and a third behind both; `order`: the primitive
@@ -59,6 +77,17 @@ def overlap(order=(0, 1, 2), duplicate=False):
     v = [at(cam, 3.25, 4.25, 1.), at(cam, 28.25, 6.25, 2.), at(cam, 9.25, 27.25, 1.5),
          at(cam, 27.25, 3.25, 1.25), at(cam, 29.25, 25.25, 1.75), at(cam, 2.25, 16.25, 2.25),
          at(cam, 1.25, 1.25, 4.), at(cam, 30.25, 2.25, 4.), at(cam, 15.25, 30.25, 3.)]
+    order = list(order[:1]) + list(order) if duplicate else list(order)
+    return case(cam, v, np.array([[0, 1, 2], [3, 4, 5], [6, 7, 8]])[order], obj_class=(1, 5, 9), face_obj=order)
+
+
+def overlap_small(order=(0, 1, 2), duplicate=False):
+    """overlap() with every clamped box within SMALL_BOX pixels (7 x 7, 8 x 6, 8 x 8): the same crossing, the same
+    reversed order and the same coplanar duplicate, each triangle walked by its own thread"""
+    cam = camera(16, 16)
+    v = [at(cam, 1.25, 1.25, 1.), at(cam, 8.25, 2.25, 2.), at(cam, 3.25, 8.25, 1.5),
+         at(cam, 8.25, 1.25, 1.25), at(cam, 8.75, 7.25, 1.75), at(cam, 1.25, 5.25, 2.25),
+         at(cam, 0.75, 0.75, 4.), at(cam, 8.75, 1.25, 4.), at(cam, 4.25, 8.75, 3.)]
     order = list(order[:1]) + list(order) if duplicate else list(order)
     return case(cam, v, np.array([[0, 1, 2], [3, 4, 5], [6, 7, 8]])[order], obj_class=(1, 5, 9), face_obj=order)
 
@@ -152,6 +181,138 @@ def ragged_scan(n=500, seed=0):
     return np.concatenate([p, p[:, 2:3]], 1).astype(np.float32)
 
 
+# 7 ------------------------------------------------------------------------------- both sides of the SMALL_BOX threshold ----
+def box_pixels(c):
+    """(F,) int: the pixels of every face's clamped box as include/rfd_render.h rule 3 defines it -- the pixels whose
+    centre 256 i + 128 lies within the snapped corners' extent, cut to the image -- from render_f64.project's snapped
+    coordinates; 0 for a face that is rejected (an invalid or missing corner, no area, an empty box)"""
+    cam, V = c['camera'], len(c['vertices'])
+    _, ix, iy, valid, _ = render_f64.project(c['vertices'], cam.params, cam.near)
+    out = np.zeros(len(c['faces']), np.int64)
+    for f, tri in enumerate(c['faces']):
+        if (tri < 0).any() or (tri >= V).any() or not valid[tri].all():
+            continue
+        x, y = [int(v) for v in ix[tri]], [int(v) for v in iy[tri]]
+        if (x[1] - x[0]) * (y[2] - y[0]) - (y[1] - y[0]) * (x[2] - x[0]) == 0:
+            continue
+        i0, i1 = max(-((128 - min(x)) // 256), 0), min((max(x) - 128) // 256, cam.width - 1)
+        j0, j1 = max(-((128 - min(y)) // 256), 0), min((max(y) - 128) // 256, cam.height - 1)
+        out[f] = max(i1 - i0 + 1, 0) * max(j1 - j0 + 1, 0)
+    return out
+
+
+def large_triangles(c):
+    """[(face, workgroup, thread)] of the faces that raster_triangles_kernel leaves to the whole workgroup"""
+    return [(int(f), int(f) // RASTER_THREADS, int(f) % RASTER_THREADS) for f in np.nonzero(box_pixels(c) > SMALL_BOX)[0]]
+
+
+# the clamped boxes of threshold()'s faces, pair by pair (the CPU tier holds the geometry to them)
+THRESHOLD_BOXES = [7 * 9, 7 * 9, 8 * 8, 8 * 8, 5 * 13, 5 * 13, 6 * 11, 6 * 11, 1 * 64, 1 * 64, 64 * 1, 64 * 1,
+                   1 * 65, 1 * 65, 65 * 1, 65 * 1, 8 * 8, 8 * 8, 13 * 5, 13 * 5]
+
+
+def threshold():
+    """pairs of triangles with the same clamped box at separate places of one 80 x 80 image, the boxes on both sides of
+    SMALL_BOX (THRESHOLD_BOXES).  The two of a pair overlap, one at depth 2 and one at depth 4 (which of them has the
+    lower index alternates), so every pixel has a definite winner.  The last two pairs are clamped by the image: one
+    reaches far out over the left and the upper border (negative snapped coordinates) and keeps 8 x 8 pixels, one reaches
+    far out over the right border and keeps 13 x 5 = 65 only because the image is 80 wide."""
+    cam = camera(80, 80, focal=64.)
+    v, faces = [], []
+
+    def pair(a, b, front_first):
+        for tri, z in ((a, 2. if front_first else 4.), (b, 4. if front_first else 2.)):
+            faces.append([len(v), len(v) + 1, len(v) + 2])
+            v.extend(at(cam, sx, sy, z) for sx, sy in tri)
+
+    def halves(x0, y0, x1, y1, front_first):
+        """the upper-left and the upper-right half of a rectangle: they share its upper quarter"""
+        pair([(x0, y0), (x1, y0), (x0, y1)], [(x0, y0), (x1, y0), (x1, y1)], front_first)
+
+    halves(16.25, 2.25, 23.25, 11.25, True)                                   # columns 16..22, rows 2..10: 7 x 9
+    halves(28.25, 2.25, 36.25, 10.25, False)                                  # 8 x 8
+    halves(40.25, 2.25, 45.25, 15.25, True)                                   # 5 x 13
+    halves(50.25, 2.25, 56.25, 13.25, False)                                  # 6 x 11
+    pair([(10.25, 10.25), (11.25, 10.25), (10.75, 74.25)], [(10.25, 74.25), (11.25, 74.25), (10.75, 10.25)], True)   # column 10, rows 10..73
+    pair([(8.25, 77.25), (8.25, 78.25), (72.25, 77.75)], [(72.25, 77.25), (72.25, 78.25), (8.25, 77.75)], False)     # row 77, columns 8..71
+    pair([(12.25, 9.25), (13.25, 9.25), (12.75, 74.25)], [(12.25, 74.25), (13.25, 74.25), (12.75, 9.25)], False)     # column 12, rows 9..73
+    pair([(8.25, 75.25), (8.25, 76.25), (73.25, 75.75)], [(73.25, 75.25), (73.25, 76.25), (8.25, 75.75)], True)      # row 75, columns 8..72
+    pair([(-120.25, -90.25), (7.75, 2.25), (2.25, 7.75)], [(-90.25, -120.25), (7.75, 3.25), (3.25, 7.75)], True)     # columns, rows 0..7
+    pair([(67.25, 30.25), (200.25, 30.25), (73.25, 35.25)], [(67.25, 30.25), (300.25, 35.25), (67.25, 35.25)], True)   # columns 67..79, rows 30..34
+    return case(cam, v, faces)
+
+
+# 8 --------------------------------------------------------------------------------------------- mixed workgroups ----
+MIXED_LARGE = (0, 255, 256, 257, 400, 511, 512, 527)         # where mixed() has its large triangles
+MIXED_TWIN = (255, 257)                                       # 257 is 255 again
+
+
+def mixed(twin=True, points=True):
+    """96 x 64.  Small: a 20 x 13 grid of quads of 4 x 4 pixels, each cut in two, at depth 2 (520 triangles with a box of
+    16 pixels).  Large: eight triangles spliced in at MIXED_LARGE -- the first and the last thread of workgroups 0 and 1,
+    two more inside workgroup 1, the first thread of workgroup 2 and, as the last face (F = 528), the thread next to the
+    first scan point's -- six of them tilted through the grid's depth, 400 larger than the image at depth 8 behind
+    everything, 257 a bit-equal twin of 255 (its own three vertices, the same numbers) in another workgroup, which must
+    win no pixel.  Points: 100 squares of 3 x 3 on a lattice, each at a depth of its own between 0.78 and 6.97: in front of
+    everything, between the layers, behind the grid.  They share workgroup 2 with the last 16 triangles.
+    twin=False leaves face 257 out (F = 527), points=False the scan."""
+    cam = camera(96, 64, focal=128.)
+    v = [at(cam, 8.25 + 4 * a, 6.25 + 4 * b, 2.) for b in range(14) for a in range(21)]
+    small = []
+    for b in range(13):
+        for a in range(20):
+            k = 21 * b + a
+            small += [[k, k + 1, k + 22], [k, k + 22, k + 21]]
+    large = {0: [(4.25, 3.25, 1.), (90.25, 10.25, 4.), (20.25, 60.25, 2.)],
+             255: [(92.25, 5.25, 1.), (10.25, 30.25, 4.), (80.25, 61.25, 4.)],
+             256: [(50.25, 2.25, 4.), (93.25, 50.25, 1.), (30.25, 62.25, 2.)],
+             400: [(-168.25, -80.25, 8.), (312.25, -48.25, 8.), (-24.25, 272.25, 8.)],
+             511: [(2.25, 40.25, 1.), (60.25, 20.25, 4.), (70.25, 63.25, 1.)],
+             512: [(30.25, 8.25, 1.), (85.25, 30.25, 2.), (40.25, 55.25, 4.)],
+             527: [(60.25, 4.25, 4.), (94.25, 40.25, 1.), (55.25, 50.25, 1.)]}
+    large[MIXED_TWIN[1]] = large[MIXED_TWIN[0]]
+    faces, small = [], iter(small)
+    for f in range(len(MIXED_LARGE) + 520):
+        if f in large:
+            faces.append([len(v), len(v) + 1, len(v) + 2])
+            v.extend(at(cam, *corner) for corner in large[f])
+        else:
+            faces.append(next(small))
+    if not twin:
+        del faces[MIXED_TWIN[1]]
+    pts = None
+    if points:
+        pts = [at(cam, 6.5 + 9 * (n % 10), 4.5 + 6 * (n // 10), 0.78125 + (37 * n % 100) / 16.) + [1.] for n in range(100)]
+    return case(cam, v, faces, points=pts, point_px=3, obj_class=(2, 6), face_obj=np.arange(len(faces)) % 2)
+
+
+# 9 ----------------------------------------------------------------------------------------- strips and point edges ----
+def strip(upright, point_px=3):
+    """an image one pixel wide, 1 x 130 (upright) or 130 x 1: a tilted triangle whose clamped box is the whole line of 130
+    pixels, two small ones in front of it (20 pixels, and exactly SMALL_BOX: it is three pixels wide before the image cuts
+    it) and points in front, in between, on both ends, just outside, outside by far and behind the camera"""
+    cam = camera(1, 130, focal=64.) if upright else camera(130, 1, focal=64.)
+    put = (lambda x, y, z: at(cam, x, y, z)) if upright else (lambda x, y, z: at(cam, y, x, z))
+    v = [put(-1.25, -3.25, 4.), put(3.25, -3.25, 4.), put(-1.25, 400.25, 2.),
+         put(-0.75, 10.25, 2.), put(1.75, 10.25, 2.), put(0.25, 30.25, 2.),
+         put(-0.75, 40.25, 2.), put(1.75, 40.25, 2.), put(0.25, 104.25, 1.)]
+    pts = [put(0.3, 5.3, 1.5), put(0.6, 129.6, 1.25), put(0.4, 64.4, 3.5), put(0.3, 20.3, 2.5), put(-1.7, 80.3, 1.75),
+           put(0.3, -1.7, 1.125), put(100.3, 7.3, 1.5), put(0.3, 300.3, 1.5), [0., 0., -1.], put(0.7, 110.3, 0.75)]
+    return case(cam, v, [[3, 4, 5], [6, 7, 8], [0, 1, 2]], points=np.concatenate([np.asarray(pts), np.ones((len(pts), 1))], 1),
+                point_px=point_px)                                             # the large one last: thread 2
+
+
+def points_63():
+    """the widest square, 63 x 63, on a 40 x 36 image: cut by all four borders at once (the point in the middle covers
+    the whole image), by two of them in the corners, reaching in from outside, outside by far, behind the camera; a
+    tilted triangle between the points' depths"""
+    cam = camera(40, 36, focal=32.)
+    v = [at(cam, 3.25, 2.25, 2.), at(cam, 37.25, 3.25, 4.), at(cam, 8.25, 33.25, 2.)]
+    pts = [at(cam, 20.3, 18.3, 6.), at(cam, 2.3, 2.3, 1.25), at(cam, 38.6, 34.6, 5.), at(cam, -20.7, 10.3, 1.125),
+           at(cam, 30.3, 60.7, 3.), at(cam, 80.3, 7.3, 1.5), [0., 0., -1.], at(cam, 25.3, 5.7, 8.)]
+    return case(cam, v, [[0, 1, 2]], points=np.concatenate([np.asarray(pts), np.ones((len(pts), 1))], 1), point_px=63)
+
+
 # ------------------------------------------------------------------------------------------- what both tiers share ----
 PALETTE = ((0.9, 0.1, 0.1), (0.1, 0.8, 0.2), (0.2, 0.3, 0.9), (0.8, 0.8, 0.1), (0.1, 0.7, 0.7), (0.7, 0.2, 0.8),
            (0.5, 0.5, 0.5), (0.9, 0.5, 0.1), (0.3, 0.6, 0.3), (0.6, 0.3, 0.3), (0.2, 0.2, 0.5), (0.4, 0.9, 0.6))
@@ -170,7 +331,44 @@ SMALL_CASES = [("shared_edge", lambda: shared_edge(False)), ("shared_edge_on_cen
                ("large_64x48", lambda: larger_than_image(64, 48)),
                ("large_1024x768", lambda: larger_than_image(1024, 768)), ("rejections", rejections),
                ("points_1", lambda: points(1)), ("points_3", lambda: points(3)),
-               ("points_5", lambda: points(5))]
+               ("points_5", lambda: points(5)),
+               ("shared_edge_small", lambda: shared_edge_small(False)),
+               ("shared_edge_small_on_centres", lambda: shared_edge_small(True)),
+               ("overlap_small", overlap_small), ("overlap_small_reversed", lambda: overlap_small(order=(2, 1, 0))),
+               ("overlap_small_duplicate", lambda: overlap_small(duplicate=True)),
+               ("threshold", threshold), ("mixed", mixed), ("mixed_no_twin", lambda: mixed(twin=False)),
+               ("mixed_no_points", lambda: mixed(points=False)),
+               ("strip_1x130", lambda: strip(True)), ("strip_130x1", lambda: strip(False)),
+               ("strip_1x130_px63", lambda: strip(True, 63)), ("strip_130x1_px63", lambda: strip(False, 63)),
+               ("points_63", points_63)]
+_restated = {}
+
+
+def restated(name):
+    """(the case of that name in SMALL_CASES, its restatement): made once and shared by the tests of both tiers, none of
+    which writes to either"""
+    if name not in _restated:
+        c = dict(SMALL_CASES)[name]()
+        _restated[name] = (c, restate(c))
+    return _restated[name]
+
+
+def winner_pairs(c, res):
+    """the (winner, loser) pairs of kinds that meet at one pixel at least, from the restatement's candidate list; a kind
+    is 'small', 'large' (box_pixels > SMALL_BOX) or 'point', and 'large+' is a large loser in another workgroup than
+    the (large) winner's"""
+    F = len(c['faces'])
+    n_points = 0 if c['points'] is None else len(c['points'])
+    kind = np.concatenate([np.where(box_pixels(c) > SMALL_BOX, 1, 0), np.full(n_points, 2)])
+    pix, _, prim = res['cand']
+    win = res['ids'].reshape(-1)[pix].astype(np.int64)
+    lost = prim != win
+    win, prim = win[lost], prim[lost]
+    names = ('small', 'large', 'point')
+    pairs = {(names[a], names[b]) for a, b in set(zip(kind[win].tolist(), kind[prim].tolist()))}
+    if ((kind[win] == 1) & (kind[prim] == 1) & (win // RASTER_THREADS != prim // RASTER_THREADS)).any():
+        pairs.add(('large', 'large+'))
+    return pairs
 
 
 def ragged_inputs(meshes):

@@ -90,7 +90,9 @@ def project(xyz, camera, near):
 def rasterise(vertices, faces, points, camera, near, width, height, point_px=3, face_obj=None, obj_class=None,
               palette=None, eye=(0., 0., 0.)):
     """vertices (V,3) f32, faces (F,3), points (N,3+) or None, camera: the 16 doubles -> {'ids' (H,W) i32, 'depth' (H,W)
-    f32, 'image' (H,W,3) u8, 'min_key_gap', 'min_snap_margin', 'candidates': how many (pixel, primitive) pairs}"""
+    f32, 'image' (H,W,3) u8, 'min_key_gap', 'min_snap_margin', 'candidates': how many (pixel, primitive) pairs,
+    'invz_bits' (H,W) i64: the bits of the winner's f32 1/z, the key's high word (0 on the background), 'cand': the
+    candidate list itself, three (candidates,) i64 arrays: pixel j W + i, bits of the f32 1/z, primitive}"""
     W, H = int(width), int(height)
     vertices = np.asarray(vertices, np.float32).reshape(-1, 3)
     faces = np.asarray(faces, np.int64).reshape(-1, 3)
@@ -155,6 +157,7 @@ def rasterise(vertices, faces, points, camera, near, width, height, point_px=3, 
     ids = np.full(H * W, -1, np.int32)
     depth = np.full(H * W, np.inf, np.float32)
     gap, n_cand = None, 0
+    invz_bits, cand = np.zeros(H * W, np.int64), (np.zeros(0, np.int64),) * 3
     if cand_pix:
         pix, bits, prim = np.concatenate(cand_pix), np.concatenate(cand_bits), np.concatenate(cand_prim)
         n_cand = len(pix)
@@ -164,6 +167,7 @@ def rasterise(vertices, faces, points, camera, near, width, height, point_px=3, 
         hit = best != 0
         win_prim = 0xffffffff - (best & 0xffffffff)
         win_bits = best >> 32
+        invz_bits, cand = win_bits, (pix, bits, prim)
         ids[hit] = win_prim[hit].astype(np.int32)
         with np.errstate(all='ignore'):
             depth[hit] = (1.0 / win_bits[hit].astype(np.uint32).view(np.float32).astype(np.float64)).astype(np.float32)
@@ -193,7 +197,7 @@ def rasterise(vertices, faces, points, camera, near, width, height, point_px=3, 
         cls = np.clip(np.asarray(obj_class, np.int64)[obj], 0, C - 1)
         image[on_face] = to_u8(pal[cls] * s[:, None])
     return {'ids': ids.reshape(H, W), 'depth': depth.reshape(H, W), 'image': image.reshape(H, W, 3), 'min_key_gap': gap,
-            'min_snap_margin': margin, 'candidates': n_cand}
+            'min_snap_margin': margin, 'candidates': n_cand, 'invz_bits': invz_bits.reshape(H, W), 'cand': cand}
 
 
 def admissible(result):

@@ -16,7 +16,7 @@ from rfdnet_amd import io, render
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import render_cases as cases  # noqa: E402
 import render_f64  # noqa: E402
-from render_cases import PALETTE, SMALL_CASES, ragged_inputs, read_png, restate  # noqa: E402
+from render_cases import PALETTE, SMALL_CASES, ragged_inputs, read_png  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -53,13 +53,19 @@ def compare(got, want):
 @pytest.mark.parametrize("name, make", SMALL_CASES, ids=[n for n, _ in SMALL_CASES])
 def test_case_matches_the_restatement(hip, name, make):
     """1 the fill rule, 2 the depth test (with the reversed order and the coplanar duplicate), 3 the large-triangle path
-    at two image sizes, 4 the rejections, 5 the points at three widths"""
-    c = make()
-    want = restate(c)
+    at two image sizes, 4 the rejections, 5 the points at three widths; then 1 and 2 again on the per-thread path
+    (*_small), boxes on both sides of SMALL_BOX, both paths and the points mixed in three workgroups, images one pixel
+    wide and the widest point square (tests/render_cases.py 7 to 9)"""
+    c, want = cases.restated(name)
     assert render_f64.admissible(want)
+    print("large triangles (face, workgroup, thread):", cases.large_triangles(c))
     ids = compare(run(c), want)
-    if name.startswith("shared_edge"):
+    if name.startswith("shared_edge_small"):
+        assert (ids >= 0).sum() == cases.shared_edge_small_pixels(name.endswith("on_centres"))
+    elif name.startswith("shared_edge"):
         assert (ids >= 0).sum() == cases.shared_edge_pixels(name.endswith("on_centres"))
+    if name in ("mixed", "mixed_no_points"):
+        assert (ids == cases.MIXED_TWIN[0]).any() and not (ids == cases.MIXED_TWIN[1]).any()
     if name.startswith("large"):
         assert (ids == 0).all()
     if name == "rejections":
@@ -68,14 +74,80 @@ def test_case_matches_the_restatement(hip, name, make):
 
 
 def test_reversed_order_relabels_and_a_duplicate_loses_to_the_lower_index(hip):
-    plain, back, dup = (run(c) for c in (cases.overlap(), cases.overlap(order=(2, 1, 0)), cases.overlap(duplicate=True)))
-    ids = plain.ids.cpu().numpy()
-    assert set(np.unique(ids)) == {-1, 0, 1, 2}
-    np.testing.assert_array_equal(np.where(back.ids.cpu().numpy() >= 0, 2 - back.ids.cpu().numpy(), -1), ids)
-    assert torch.equal(back.image, plain.image) and torch.equal(back.depth, plain.depth)
-    d = dup.ids.cpu().numpy()
-    assert 1 not in d
-    np.testing.assert_array_equal(np.where(d > 0, d - 1, d), ids)
+    for overlap in (cases.overlap, cases.overlap_small):             # on the shared path, on the per-thread path
+        plain, back, dup = (run(c) for c in (overlap(), overlap(order=(2, 1, 0)), overlap(duplicate=True)))
+        ids = plain.ids.cpu().numpy()
+        assert set(np.unique(ids)) == {-1, 0, 1, 2}
+        np.testing.assert_array_equal(np.where(back.ids.cpu().numpy() >= 0, 2 - back.ids.cpu().numpy(), -1), ids)
+        assert torch.equal(back.image, plain.image) and torch.equal(back.depth, plain.depth)
+        d = dup.ids.cpu().numpy()
+        assert 1 not in d
+        np.testing.assert_array_equal(np.where(d > 0, d - 1, d), ids)
+
+
+# ---------------------------------------------------------------------- both triangle paths and the points in one launch ----
+def same_bits(a, b):
+    return all(torch.equal(x, y) for x, y in zip(a, b))
+
+
+def reordered(c, face_order, point_order):
+    """the case with its primitives in another order: new face k is old face face_order[k], points likewise"""
+    return dict(c, faces=c['faces'][face_order], face_obj=c['face_obj'][face_order], points=c['points'][point_order])
+
+
+@pytest.mark.parametrize("order", ["reversed", "permuted"])
+def test_mixed_does_not_depend_on_who_draws_what(hip, order):
+    """another primitive order gives every triangle another thread, another workgroup and other neighbours in it, and a
+    large one other company in the workgroup's list: the ids follow the order, depth and picture keep every bit"""
+    c, want = cases.restated("mixed_no_twin")
+    F, N = len(c['faces']), len(c['points'])
+    if order == "reversed":
+        face_order, point_order = np.arange(F)[::-1].copy(), np.arange(N)[::-1].copy()
+    else:
+        rng = np.random.default_rng(5)
+        face_order, point_order = rng.permutation(F), rng.permutation(N)
+    moved = reordered(c, face_order, point_order)
+    print("large triangles (face, workgroup, thread):", cases.large_triangles(moved))
+    assert cases.large_triangles(moved) != cases.large_triangles(c)
+    plain, got = run(c), run(moved)
+    ids = got.ids.cpu().numpy()
+    back = np.concatenate([[-1], face_order, F + point_order])                 # new id -> old id, -1 -> -1
+    np.testing.assert_array_equal(back[ids + 1], want['ids'])
+    assert torch.equal(got.depth, plain.depth) and torch.equal(got.image, plain.image)
+
+
+def test_mixed_twice_and_with_the_scan_read_in_place(hip):
+    c, want = cases.restated("mixed")
+    scene, pts = device_scene(c)
+    draw = lambda p: render.render_scene(scene, p, c['camera'], palette=PALETTE, point_px=c['point_px'])
+    first = draw(pts)
+    compare(first, want)
+    assert same_bits(first, draw(pts))
+    # the scan as columns 2..5 of a wider buffer: rows 9 floats apart, the first one 8 bytes into the allocation
+    buf = torch.full((pts.shape[0], 9), float('nan'), device=pts.device)
+    buf[:, 2:6] = pts
+    view = buf[:, 2:6]
+    assert view.stride() == (9, 1) and view.data_ptr() == buf.data_ptr() + 8 and not view.is_contiguous()
+    assert same_bits(first, draw(view)) and same_bits(first, draw(view.contiguous()))
+
+
+def test_rasterise_on_a_reused_scratch_gives_the_restated_keys(hip):
+    """watertight()'s route: render.rasterise with point_px = 1, no points and the scratch of the call before"""
+    c, want = cases.restated("mixed_no_points")
+    scene, _ = device_scene(c)
+    cam = c['camera']
+    scratch = render.rasterise(scene.vertices, scene.faces, cam.params, cam.near, cam.width, cam.height, point_px=1)
+    first = scratch.keys.clone()
+    again = render.rasterise(scene.vertices, scene.faces, cam.params, cam.near, cam.width, cam.height, point_px=1,
+                             scratch=scratch)
+    assert again.keys.data_ptr() == scratch.keys.data_ptr() and torch.equal(again.keys, first)
+    keys = first.cpu().numpy()
+    assert keys.dtype == np.int64 and keys.shape == want['ids'].shape and (keys > 0).all()
+    np.testing.assert_array_equal(0xffffffff - (keys & 0xffffffff), want['ids'])
+    step = np.abs((keys >> 32) - want['invz_bits'])
+    print("1/z: max %d ulp" % step.max())
+    assert (step <= 1).all()
+    assert not (0xffffffff - (keys & 0xffffffff) == cases.MIXED_TWIN[1]).any()
 
 
 @pytest.fixture(scope="module")

@@ -22,10 +22,11 @@ from mc_ref import index_soup, marching_cubes_soup  # noqa: E402
 # ------------------------------------------------------------------------------------------------ admissibility ----
 @pytest.mark.parametrize("name, make", SMALL_CASES, ids=[n for n, _ in SMALL_CASES])
 def test_every_case_is_admissible(name, make):
-    res = restate(make())
+    c, res = cases.restated(name)
     print(name, res['min_key_gap'], res['min_snap_margin'], res['candidates'])
     assert render_f64.admissible(res), (res['min_key_gap'], res['min_snap_margin'])
     assert (res['ids'] >= 0).any()
+    print("large triangles (face, workgroup, thread):", cases.large_triangles(c))
 
 
 def test_the_restatement_covers_a_shared_edge_once_and_breaks_ties_by_index():
@@ -33,16 +34,111 @@ def test_the_restatement_covers_a_shared_edge_once_and_breaks_ties_by_index():
         res = restate(cases.shared_edge(on_centres))
         assert res['candidates'] == (res['ids'] >= 0).sum() == cases.shared_edge_pixels(on_centres)
         assert set(np.unique(res['ids'])) == {-1, 0, 1}
+        res = restate(cases.shared_edge_small(on_centres))
+        assert res['candidates'] == (res['ids'] >= 0).sum() == cases.shared_edge_small_pixels(on_centres)
+        assert set(np.unique(res['ids'])) == {-1, 0, 1}
     assert restate(cases.shared_edge(True))['ids'][2, 2] >= 0 and restate(cases.shared_edge(True))['ids'][13, 13] == -1
-    dup = restate(cases.overlap(duplicate=True))
-    plain = restate(cases.overlap())
-    assert 1 not in dup['ids']                                     # face 1 is face 0 again: the lower index wins
-    np.testing.assert_array_equal(np.where(dup['ids'] > 0, dup['ids'] - 1, dup['ids']), plain['ids'])
-    back = restate(cases.overlap(order=(2, 1, 0)))
-    np.testing.assert_array_equal(np.where(back['ids'] >= 0, 2 - back['ids'], -1), plain['ids'])
-    np.testing.assert_array_equal(back['image'], plain['image'])
+    assert restate(cases.shared_edge_small(True))['ids'][2, 2] >= 0 and restate(cases.shared_edge_small(True))['ids'][9, 9] == -1
+    for overlap in (cases.overlap, cases.overlap_small):
+        dup = restate(overlap(duplicate=True))
+        plain = restate(overlap())
+        assert set(np.unique(plain['ids'])) == {-1, 0, 1, 2}
+        assert 1 not in dup['ids']                                 # face 1 is face 0 again: the lower index wins
+        np.testing.assert_array_equal(np.where(dup['ids'] > 0, dup['ids'] - 1, dup['ids']), plain['ids'])
+        back = restate(overlap(order=(2, 1, 0)))
+        np.testing.assert_array_equal(np.where(back['ids'] >= 0, 2 - back['ids'], -1), plain['ids'])
+        np.testing.assert_array_equal(back['image'], plain['image'])
     rej = restate(cases.rejections())
     assert set(np.unique(rej['ids'])) == {-1, 0, 1, 2}
+
+
+# ------------------------------------------------------------------------------- which path draws which triangle ----
+def test_the_small_scenes_stay_on_the_per_thread_path_and_the_old_ones_on_the_shared_path():
+    """the fill rule and the ties are tested once on each path: every box of the *_small scenes is within SMALL_BOX
+    (the shared-edge halves exactly on it), every drawn box of the scenes they were shrunk from is beyond it"""
+    for on_centres in (False, True):
+        assert cases.box_pixels(cases.shared_edge_small(on_centres)).tolist() == [cases.SMALL_BOX] * 2
+        assert (cases.box_pixels(cases.shared_edge(on_centres)) > cases.SMALL_BOX).all()
+    for kwargs in ({}, {'order': (2, 1, 0)}, {'duplicate': True}):
+        small, large = cases.box_pixels(cases.overlap_small(**kwargs)), cases.box_pixels(cases.overlap(**kwargs))
+        assert (small > 0).all() and (small <= cases.SMALL_BOX).all() and (large > cases.SMALL_BOX).all()
+    assert sorted(cases.box_pixels(cases.overlap_small()).tolist()) == [48, 49, 64]
+    rej = cases.box_pixels(cases.rejections())
+    assert (rej[:3] > 0).all() and not rej[3:].any()                # 0 for whatever rule 2 or 3 rejects
+
+
+def test_threshold_has_the_boxes_it_is_named_for():
+    c, res = cases.restated("threshold")
+    boxes = cases.box_pixels(c)
+    assert boxes.tolist() == cases.THRESHOLD_BOXES
+    assert sorted(set(boxes.tolist())) == [63, 64, 65, 66]
+    _, ix, iy, _, _ = render_f64.project(c['vertices'], c['camera'].params, c['camera'].near)
+    far_out = c['faces'][16:18]                                     # the pair that the left and the upper border cut
+    assert (ix[far_out].min(1) < -80 * 256).all() and (iy[far_out].min(1) < -80 * 256).all()
+    assert (ix[c['faces'][18:]].max(1) > 2 * 80 * 256).all()        # the pair that the right border cuts
+    # unclamped, the last pair's boxes would have 5 rows of 133 and 233 pixels: 13 x 5 is the image's width at work
+    wins = np.bincount(res['ids'][res['ids'] >= 0], minlength=20)
+    print("pixels won:", wins.tolist())
+    assert (wins > 0).all()                                         # both of every pair show
+    for a in range(0, 20, 2):                                       # and the nearer one owns all it covers
+        pix, bits, prim = res['cand']
+        front = a if c['vertices'][c['faces'][a, 0], 2] == 2. else a + 1
+        assert (res['ids'].reshape(-1)[pix[prim == front]] == front).all()
+
+
+def test_mixed_puts_both_paths_and_the_points_side_by_side():
+    c, res = cases.restated("mixed")
+    F, N = len(c['faces']), len(c['points'])
+    assert (F, N) == (528, 100) and F % cases.RASTER_THREADS == 16          # workgroup 2: 16 triangles, then points
+    boxes = cases.box_pixels(c)
+    assert tuple(np.nonzero(boxes > cases.SMALL_BOX)[0]) == cases.MIXED_LARGE
+    assert (boxes[boxes <= cases.SMALL_BOX] == 16).all()
+    assert [(w, t) for _, w, t in cases.large_triangles(c)] == [(0, 0), (0, 255), (1, 0), (1, 1), (1, 144), (1, 255),
+                                                                (2, 0), (2, 15)]
+    assert boxes[400] == 96 * 64                                             # larger than the image
+    first, twin = cases.MIXED_TWIN
+    for name in ("mixed", "mixed_no_points"):
+        ids = cases.restated(name)[1]['ids']
+        assert (ids == first).sum() > 100 and (ids == twin).sum() == 0       # the twin wins nothing
+    np.testing.assert_array_equal(c['vertices'][c['faces'][first]], c['vertices'][c['faces'][twin]])
+    assert not set(c['faces'][first]) & set(c['faces'][twin])                # its own vertices, the same numbers
+    ids = res['ids'].reshape(-1)
+    kinds = [(ids < 0).sum(), (boxes[ids[(ids >= 0) & (ids < F)]] <= cases.SMALL_BOX).sum(),
+             (boxes[ids[(ids >= 0) & (ids < F)]] > cases.SMALL_BOX).sum(), (ids >= F).sum()]
+    print("winners: background %d, small %d, large %d, point %d" % tuple(kinds))
+    assert min(kinds[1:]) > 200
+    for f in cases.MIXED_LARGE:
+        assert f == twin or (ids == f).sum() > 100, f                        # every other large triangle shows
+    z = c['points'][:, 2]
+    assert len(np.unique(z)) == N and (z < 1.).any() and ((z > 2.) & (z < 8.)).any()
+    pairs = cases.winner_pairs(c, res)
+    print(sorted(pairs))
+    for pair in (('small', 'large'), ('large', 'small'), ('large', 'large+'), ('point', 'large'), ('large', 'point'),
+                 ('small', 'point'), ('point', 'small')):
+        assert pair in pairs, pair
+    # without the twin the other seven keep their neighbours: one index lower from 257 on
+    no_twin = cases.restated("mixed_no_twin")[0]
+    assert [f for f, _, _ in cases.large_triangles(no_twin)] == [0, 255, 256, 399, 510, 511, 526]
+
+
+def test_strips_and_wide_points_are_what_they_are_named_for():
+    for upright in (True, False):
+        c, res = cases.restated("strip_1x130" if upright else "strip_130x1")
+        assert (c['camera'].width, c['camera'].height) == ((1, 130) if upright else (130, 1))
+        assert cases.box_pixels(c).tolist() == [20, cases.SMALL_BOX, 130]
+        ids = np.unique(res['ids'])
+        assert {0, 1, 2} <= set(ids) and (ids >= 3).sum() >= 3 and ids.min() >= 0
+        wide = cases.restated("strip_1x130_px63" if upright else "strip_130x1_px63")[1]
+        assert (wide['ids'] >= 3).sum() > (res['ids'] >= 3).sum()
+    c, res = cases.restated("points_63")
+    F, (H, W) = 1, res['ids'].shape
+    centre, corner, other_corner, from_outside, from_below, far, behind, back = (F + n for n in range(8))
+    pix, _, prim = res['cand']
+    assert (prim == centre).sum() == H * W                                   # cut by all four borders at once
+    for n, rows, cols in ((corner, 34, 34), (other_corner, 33, 33), (from_outside, 36, 11), (from_below, 7, 40)):
+        assert (prim == n).sum() == rows * cols, n                           # ... by two, by three of them
+    assert not np.isin(prim, (far, behind)).any()
+    assert {0, corner, other_corner, from_outside, from_below} <= set(np.unique(res['ids']))
 
 
 def sphere_meshes():
