@@ -66,6 +66,41 @@ int rfd_mesh_iou_counts(int P, int G,
 int rfd_mesh_iou_finalize(int P, int G, const int *counts, const int *cnt_p, const int *cnt_g,
                           const int *rows_p, const int *rows_g, int K_out, int G_out, double *iou, void *stream);
 
+/* ---- The ragged batch: M1 - M2 for ALL N objects of a scene in a number of launches that does not depend on N
+ * (csrc/objgrid.hip; restated in numpy in tests/objgrid_ref.py).  The result is what the per-object path
+ * (mesh_sample's voxelisers, then rfd_objgrid_pack per object) gives: rules M1 - M2 above and C1 - C6 / V1 - V4 of
+ * rfd_sample.h, applied per object.  New is how the lattice is walked and how triangles are filtered.  Float64 unless
+ * stated, left to right as written, no fused multiply-add.
+ *   B1 frames.   On the host, from one read-back: M1 per object gives lo, L, D, cell; the unit map is
+ *                (v - lo) / L - 0.5 for all objects at once.  An object has a grid iff it has vertices and faces and M1
+ *                yields a frame.  Triangles of an object without a grid are read by no kernel.
+ *   B2 surface.  V1: the corners are ((u + 0.5) * D_k)[faces] in f64, rounded once to f32; D_k enters as a double.
+ *                V2 - V4 with R = D_k of the triangle's object.  A set voxel (i, j, z) sets bit z & 63 of word
+ *                off_k + (i * D + j) * W + (z >> 6) of the surface words S.
+ *   B3 constants.  C1 at res = 512 per object, on the bounding box of the object's referenced corners in the unit cube:
+ *                host, float64, from the same read-back, uploaded as a table (N,6) = scale[3], translate[3].  An object
+ *                whose box lacks positive extent on some axis has I = 0; its row holds zeros, and a row whose scale is
+ *                not positive on every axis has no interior.  A scale or translate that is not finite is refused on the
+ *                host.
+ *   B4 lattice.  The coordinate of index i on any axis is c_i = (i + 0.5) / D - 0.5 (one division, one subtraction) and
+ *                its image is p' = s * c_i + t (C2).  Column (i, j) is a candidate iff 0 <= px' < 512 and 0 <= py' < 512;
+ *                a z index is a candidate iff 0 <= pz' <= 512; both decided on the doubles before any conversion.
+ *   B5 parity.   A triangle that passes C4 for (px', py') and has n2 != 0 yields depth (C5).  For every candidate z,
+ *                rhs = pz'_z * |n2|: depth >= rhs toggles bit z of P0, depth < rhs toggles bit z of P1, a NaN toggles
+ *                neither.  I = P0 & P1.  The order in which a column meets its triangles is free.
+ *   B6 filter.   A column looks only at triangles whose C3 cell box contains the column's cell ((int)px', (int)py'), or
+ *                at any superset of them (C3: the cells only filter).  Here: per object 32 x 32 bins, bin = cell >> 4 per
+ *                axis; a triangle goes into the bins of its C3 box shifted the same way; the lists are a CSR over all
+ *                N * 1024 bins (bin index (k * 32 + bx) * 32 + by) built in two passes of integer atomics, the prefix
+ *                between them is the caller's.  No per-object res^2 array.
+ *   B7 union.    U = S | I word by word; cnt[k] = (popcount U, popcount S) by integer adds.
+ *
+ * The table.  dim (N) i32 (0: no grid), off (N) i64, both ALSO as host arrays (dim_host, off_host): every launcher reads
+ * the host copy and refuses -- hipErrorInvalidValue, nothing launched -- a negative count, N > 65535, a null pointer it
+ * needs, a dim outside {0} and [2, 256], and off < 0 or off + D * D * W > n_words.  The kernels check the device rows and
+ * face_obj again: a row out of range is an object without a grid, a face of no such object is skipped.  F == 0, N == 0
+ * or no object with a grid: success without a launch.  The four entries are declared in rfd_objgrid.h. */
+
 #ifdef __cplusplus
 }
 #endif

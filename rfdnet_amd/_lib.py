@@ -18,7 +18,7 @@ _sz = C.c_size_t
 _d = C.c_double
 
 # name -> (restype, argtypes[, OPTIONAL]): exactly the prototypes of include/rfd_pointnet2.h / rfd_occ.h /
-# rfd_chamfer.h / rfd_eval.h / rfd_latent.h / rfd_loss.h / rfd_fit.h / rfd_render.h / rfd_decimate.h / rfd_simplify.h / rfd_fuse.h / rfd_sample.h / rfd_labels.h / rfd_mesh_eval.h.  OPTIONAL marks the test hooks, which a deployment build (RFD_NO_TEST_HOOKS=1, build.py)
+# rfd_chamfer.h / rfd_eval.h / rfd_latent.h / rfd_loss.h / rfd_fit.h / rfd_render.h / rfd_decimate.h / rfd_simplify.h / rfd_fuse.h / rfd_sample.h / rfd_labels.h / rfd_mesh_eval.h / rfd_objgrid.h.  OPTIONAL marks the test hooks, which a deployment build (RFD_NO_TEST_HOOKS=1, build.py)
 # leaves out.
 OPTIONAL = "optional"
 ABI = {
@@ -130,6 +130,10 @@ ABI = {
     "rfd_labels_sample": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _d, _d, _fl, C.POINTER(C.c_double), _f, _f, _f, _f, _f,
                                _f, _f, _f, _f]),
     "rfd_objgrid_pack": (_i, [_i, _f, _f, _f, C.c_longlong, C.c_longlong, _f, _f]),
+    "rfd_objgrid_surface": (_i, [_i, _f, _f, _i, _f, _f, _f, _f, C.c_longlong, _f, _f]),
+    "rfd_objgrid_bins": (_i, [_i, _f, _f, _i, _f, _f, _f, _f, _f, _i, _f]),
+    "rfd_objgrid_interior": (_i, [_i, _f, _i, _f, _f, _f, _f, C.c_longlong, _f, _f, _f, _i, _f, _f]),
+    "rfd_objgrid_finish": (_i, [_i, _f, _f, _f, _f, C.c_longlong, _f, _f, _f, _f]),
     "rfd_mesh_iou_counts": (_i, [_i, _i, _f, _f, _f, _f, C.c_longlong, _f, _f, _f, _f, C.c_longlong, _f, _f]),
     "rfd_mesh_iou_finalize": (_i, [_i, _i, _f, _f, _f, _f, _f, _i, _i, _f, _f]),
     "rfd_last_error_string": (C.c_char_p, []),

@@ -17,8 +17,11 @@ program and its carving is not reproduced; a world point is looked up with `floo
 voxel centre (they differ only exactly on a cell boundary); a detection that takes part but has no mesh has mesh IoU 0
 with everything, where the reference raises ValueError.
 
-Each object is voxelised on its own by the existing voxelisers, which costs a few host synchronisations per object
-(MeshIntersector); tools/mesh_eval_cost.py measures them beside the pack and the IoU kernel.
+voxelize_objects has two paths that give the same bits.  'batched' (the default; rules B1 - B7 of the header,
+csrc/objgrid.hip) voxelises all objects of a scene in one ragged batch: five launches and two read-backs whatever their
+number.  'per_object' voxelises each object on its own by mesh_sample's voxelisers, a few host synchronisations per
+object (MeshIntersector), and packs it; it is the cross-check.  tools/mesh_eval_cost.py measures both beside the IoU
+kernel.
 """
 import os
 
@@ -33,6 +36,8 @@ from .generator import Mesh
 VOXEL_SIZE = 0.047       # ap_helper.py:267, :371
 MAX_DIM = 256
 MAX_PRED, MAX_GT = 1024, 256     # rfd_ap_match's limits
+MAX_OBJECTS = 65535              # one batch of rfd_objgrid_*
+HASH_RESOLUTION, BINS = 512, 32  # rules B3 and B6
 
 
 def object_frame(lo, hi, voxel_size=VOXEL_SIZE):
@@ -72,6 +77,18 @@ class ObjectGrids(object):
     @property
     def device(self):
         return self.words.device
+
+    def grid(self, i):
+        """-> U of object i as a (D,D,D) bool tensor, unpacked on the device; None for an object without a grid"""
+        D = int(self.dims[i])
+        if D == 0:
+            return None
+        W = (D + 63) // 64
+        # the host's offsets are those of the table: assigned in object order
+        at = sum(words_of(int(d)) for d in self.dims[:i])
+        w = self.words[at:at + D * D * W].view(D, D, W, 1)
+        bits = (w >> torch.arange(64, device=w.device)) & 1
+        return bits.reshape(D, D, W * 64)[:, :, :D].bool()
 
 
 @torch.no_grad()
@@ -156,9 +173,131 @@ def object_grids(scene_mesh, voxel_size=VOXEL_SIZE):
     return out
 
 
-def voxelize_objects(scene_mesh, voxel_size=VOXEL_SIZE):
-    """SceneMesh (scene.place_objects / place_in_corners) -> ObjectGrids, one row per object"""
-    return pack_grids(object_grids(scene_mesh, voxel_size), scene_mesh.vertices.device)
+class BatchedWords(object):
+    """What batched_words leaves on the device before the union: the table (frame (N,4) f64, dims (N) i32 and off (N)
+    i64 as numpy, dim / off their device copies) and the surface and interior words S, I (n_words) i64."""
+
+    def __init__(self, frame, dims, off, dim, off_dev, S, I):
+        self.frame, self.dims, self.off, self.dim, self.off_dev, self.S, self.I = frame, dims, off, dim, off_dev, S, I
+
+    def table(self):
+        """the table arguments of the rfd_objgrid_* launchers: N, the host copy, the device copy, n_words"""
+        return (len(self.dims), self.dims.ctypes.data, self.off.ctypes.data, self.dim.data_ptr(), self.off_dev.data_ptr(),
+                int(self.S.numel()))
+
+
+def _extents(values, owner, N, spread=256):
+    """values (n,C) f64, owner (n) i64 in [0, N) -> (lo, hi) (N,C): the minimum and maximum of every owner's rows, +inf /
+    -inf for an owner without rows; a NaN goes through.  scatter_reduce's atomics serialise on one address, and a scene
+    has few objects and millions of rows, so every owner's rows are dealt over `spread` slots first."""
+    n, C = values.shape
+    slot = (owner * spread + torch.arange(n, device=values.device) % spread)[:, None].expand(-1, C)
+    start = lambda sign: torch.full((N * spread, C), sign * np.inf, dtype=values.dtype, device=values.device)
+    return (start(1).scatter_reduce(0, slot, values, 'amin').view(N, spread, C).amin(1),
+            start(-1).scatter_reduce(0, slot, values, 'amax').view(N, spread, C).amax(1))
+
+
+@torch.no_grad()
+def batched_words(scene_mesh, voxel_size=VOXEL_SIZE):
+    """Rules B1 - B6 of include/rfd_mesh_eval.h for every object of a SceneMesh at once -> BatchedWords.  Two read-backs
+    whatever the number of objects: the frames (with the offsets, the bounding boxes of the referenced corners and the
+    range of every object's face indices: everything the host decides on), and the number of (bin, triangle) pairs.
+    At most four launches: the surface, the two passes of the bins, the interior."""
+    _lib.need_gpu(scene_mesh.vertices)
+    dev = scene_mesh.vertices.device
+    N = int(scene_mesh.obj_off.numel()) - 1
+    V, F = int(scene_mesh.vertices.shape[0]), int(scene_mesh.faces.shape[0])
+    if N > MAX_OBJECTS:
+        raise ValueError("mesh IoU: %d objects in one batch, at most %d" % (N, MAX_OBJECTS))
+    up = lambda a: torch.from_numpy(a).to(dev)
+    if N <= 0:
+        empty = torch.zeros(1, dtype=torch.int64, device=dev)
+        return BatchedWords(np.zeros((0, 4)), np.zeros(0, np.int32), np.zeros(0, np.int64), up(np.zeros(0, np.int32)),
+                            up(np.zeros(0, np.int64)), empty, empty.clone())
+    v = scene_mesh.vertices.double()
+    seg = torch.bucketize(torch.arange(V, device=dev), scene_mesh.obj_off[1:].long(), right=True).clamp(max=N - 1)
+    # amin / amax let a NaN through (an object of zero extent is NaN after the placement): it then has no grid
+    lo, hi = _extents(v, seg, N)
+    L = (hi - lo).amax(1)
+    unit = (v - lo[seg]) / L[seg, None] - 0.5                                      # B1's map, for all objects at once
+    faces = scene_mesh.faces.long().reshape(-1, 3)
+    face_obj = scene_mesh.face_obj.long()
+    # the gathers run on clamped indices: they cannot leave the vertex array, whatever the faces hold
+    tri = unit[faces.clamp(0, max(V - 1, 0))] if F and V else unit.new_zeros(F, 3, 3)
+    # per face first (the minimum of minima is the minimum), then per object
+    tlo, thi = _extents(tri.amin(1), face_obj, N)[0], _extents(tri.amax(1), face_obj, N)[1]
+    flo, fhi = _extents(faces.amin(1, keepdim=True).double(), face_obj, N)[0], \
+        _extents(faces.amax(1, keepdim=True).double(), face_obj, N)[1]
+    host = torch.cat([torch.cat([lo, hi, tlo, thi, flo, fhi], 1).reshape(-1),
+                      scene_mesh.obj_off.double(), scene_mesh.face_off.double()]).cpu().numpy()      # THE read-back
+    stats = host[:14 * N].reshape(N, 14)
+    obj_off = host[14 * N:14 * N + N + 1].astype(np.int64)
+    face_off = host[14 * N + N + 1:].astype(np.int64)
+    dims, off, frame, consts = np.zeros(N, np.int32), np.zeros(N, np.int64), np.zeros((N, 4)), np.zeros((N, 6))
+    total = 0
+    for k in range(N):
+        n_v, n_f = int(obj_off[k + 1] - obj_off[k]), int(face_off[k + 1] - face_off[k])
+        fr = object_frame(stats[k, 0:3], stats[k, 3:6], voxel_size) if n_v > 0 and n_f > 0 else None
+        if fr is None:
+            continue
+        first, last = stats[k, 12] - obj_off[k], stats[k, 13] - obj_off[k]
+        if first < 0 or last >= n_v:
+            raise ValueError("mesh: face indices in [%d, %d], but %d vertices" % (first, last, n_v))
+        lo_k, _, cell, D = fr
+        dims[k], off[k] = D, total
+        frame[k, :3], frame[k, 3] = lo_k, cell
+        total += words_of(D)
+        if (stats[k, 9:12] - stats[k, 6:9] > 0).all():                             # else: flat, no interior (B3)
+            consts[k, :3], consts[k, 3:] = mesh_sample.rescale_constants(stats[k, 6:9], stats[k, 9:12], HASH_RESOLUTION)
+    S = torch.zeros(max(total, 1), dtype=torch.int64, device=dev)
+    I = torch.zeros_like(S)
+    out = BatchedWords(frame, dims, off, up(dims), up(off), S, I)
+    if total == 0:
+        return out
+    fo32 = scene_mesh.face_obj.to(torch.int32).contiguous()
+    # rule B2 / V1: ((u + 0.5) * D_k)[faces] in f64, rounded once to f32
+    tri32 = ((unit + 0.5) * up(dims.astype(np.float64))[seg, None])[faces.clamp(0, V - 1)].float().contiguous()
+    _lib.call("rfd_objgrid_surface", dev, F, tri32.data_ptr(), fo32.data_ptr(), *out.table(), S.data_ptr())
+    if not consts.any():
+        return out
+    tri, consts_dev = tri.contiguous(), up(consts)
+    count = torch.zeros(N * BINS * BINS, dtype=torch.int32, device=dev)
+    bins = lambda cursor, lst, n: _lib.call("rfd_objgrid_bins", dev, F, tri.data_ptr(), fo32.data_ptr(), N, dims.ctypes.data,
+                                            out.dim.data_ptr(), consts_dev.data_ptr(), cursor.data_ptr(), _lib.ptr(lst), n)
+    bins(count, None, 0)
+    offsets = torch.zeros(N * BINS * BINS + 1, dtype=torch.int64, device=dev)
+    offsets[1:] = torch.cumsum(count, 0, dtype=torch.int64)
+    n_pairs = int(offsets[-1])                                                      # the second read-back
+    mesh_sample.check_sizes(bin_triangle_pairs=n_pairs)                             # before anything is allocated
+    if n_pairs == 0:
+        return out
+    offsets = offsets.to(torch.int32)
+    lst = torch.empty(n_pairs, dtype=torch.int32, device=dev)
+    bins(offsets[:-1].clone(), lst, n_pairs)
+    _lib.call("rfd_objgrid_interior", dev, F, tri.data_ptr(), *out.table(), consts_dev.data_ptr(), offsets.data_ptr(),
+              lst.data_ptr(), n_pairs, I.data_ptr())
+    return out
+
+
+@torch.no_grad()
+def voxelize_batched(scene_mesh, voxel_size=VOXEL_SIZE):
+    """batched_words, then rule B7 (one rfd_objgrid_finish launch) -> ObjectGrids"""
+    b = batched_words(scene_mesh, voxel_size)
+    dev = b.S.device
+    cnt = torch.zeros(len(b.dims), 2, dtype=torch.int32, device=dev)
+    _lib.call("rfd_objgrid_finish", dev, *b.table(), b.S.data_ptr(), b.I.data_ptr(), cnt.data_ptr())
+    return ObjectGrids(torch.from_numpy(b.frame).to(dev), b.dim, b.off_dev, cnt, b.S, b.dims)
+
+
+def voxelize_objects(scene_mesh, voxel_size=VOXEL_SIZE, method='batched'):
+    """SceneMesh (scene.place_objects / place_in_corners) -> ObjectGrids, one row per object.  method: 'batched' (all
+    objects in one ragged batch: csrc/objgrid.hip, launches and read-backs independent of their number) or
+    'per_object' (one object at a time through mesh_sample's voxelisers and rfd_objgrid_pack); the same bits."""
+    if method == 'batched':
+        return voxelize_batched(scene_mesh, voxel_size)
+    if method == 'per_object':
+        return pack_grids(object_grids(scene_mesh, voxel_size), scene_mesh.vertices.device)
+    raise ValueError("voxelize_objects: method is 'batched' or 'per_object', got %r" % (method,))
 
 
 def _check_counts(P, G):
@@ -210,14 +349,16 @@ def _as_mesh(m, device):
 
 
 @torch.no_grad()
-def scene_mesh_iou(meshes, proposal_ids, parsed_predictions, parsed_gts, gt_meshes, voxel_size=VOXEL_SIZE):
+def scene_mesh_iou(meshes, proposal_ids, parsed_predictions, parsed_gts, gt_meshes, voxel_size=VOXEL_SIZE,
+                   method='batched'):
     """The mesh IoU matrix of ONE scene (the reference asserts bsize == 1 too) -> (1,K,G) f64 on the device, what
     evaluation.scene_records takes as `mesh_iou`.
     meshes, proposal_ids: the generated meshes and their proposals (ISCNet.generate); they are placed in
     parsed_predictions['pred_corners_3d_upright_camera'] (1,K,8,3), the boxes that are scored.
     gt_meshes: one (vertices, faces) (or an object with these attributes) per ground-truth row with
     box_label_mask == 1, in row order; None for a missing mesh.  They are placed in the ground-truth corners.
-    A proposal without a generated mesh, and a ground truth without one, keep IoU 0 with everything."""
+    A proposal without a generated mesh, and a ground truth without one, keep IoU 0 with everything.
+    method: voxelize_objects' ('batched' or 'per_object')."""
     corners = parsed_predictions['pred_corners_3d_upright_camera']
     _lib.need_gpu(corners)
     dev = corners.device
@@ -238,7 +379,7 @@ def scene_mesh_iou(meshes, proposal_ids, parsed_predictions, parsed_gts, gt_mesh
     pred = scene_module.place_objects([_as_mesh(m, dev) for m in meshes], ids.view(1, -1, 1), parsed_predictions)
     gt_cls = _lib.as_tensor(parsed_gts['sem_cls_label'], dev, torch.int32)[0][rows_g]
     gt = scene_module.place_in_corners([_as_mesh(m, dev) for m in gt_meshes], gt_corners[0][rows_g], gt_cls)
-    pg, gg = voxelize_objects(pred, voxel_size), voxelize_objects(gt, voxel_size)
+    pg, gg = voxelize_objects(pred, voxel_size, method), voxelize_objects(gt, voxel_size, method)
     scatter_iou(pg, gg, mesh_iou_counts(pg, gg), iou[0], ids, rows_g)
     return iou
 
