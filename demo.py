@@ -46,6 +46,10 @@ def build_parser():
     ap.add_argument("--shapenet_path", type=str, default=None,
                     help="--mode test with --gt: the directory of the ground-truth meshes (<catid>/<id>.off for the "
                          "scan's shapenet_catids / shapenet_ids arrays); also prints the mesh AP / recall of the scene")
+    ap.add_argument("--mesh_distance", action="store_true",
+                    help="--mode test with --gt and --shapenet_path: also prints the surface metrics of every selected "
+                         "proposal against its ground-truth mesh (Chamfer distance, F-score, normal consistency, ...: "
+                         "rfdnet_amd/mesh_distance.py), as per-class means")
     ap.add_argument("--mean_size_npz", type=str, default=None,
                     help="class mean sizes (the reference's datasets/scannet/scannet_means.npz); default: "
                          "$RFD_MEAN_SIZE_NPZ or that path relative to the working directory")
@@ -150,7 +154,10 @@ def main():
             rows = np.nonzero(data['box_label_mask'][0].cpu().numpy() == 1)[0]
             names = [np.asarray(gt[k]).reshape(-1)[rows] for k in ('shapenet_catids', 'shapenet_ids')]
             data['gt_meshes'] = load_gt_meshes(args.shapenet_path, *names)
-        end_points, ids, meshes, records = net.evaluate(data, completion=completion, losses=losses, mesh=with_meshes)
+        if args.mesh_distance and not with_meshes:
+            raise SystemExit("--mesh_distance needs the ground-truth meshes (--shapenet_path)")
+        end_points, ids, meshes, records = net.evaluate(data, completion=completion, losses=losses, mesh=with_meshes,
+                                                        mesh_distance=args.mesh_distance)
     else:
         end_points, ids, meshes = net.generate(data, selection=args.selection)
     if args.post_processing and gt is None and len(meshes) and 'parsed_predictions' in end_points:
@@ -167,6 +174,11 @@ def main():
         calc.step(records)
         for thr, metrics in zip((0.25, 0.5), calc.compute_metrics()):
             print('IoU %g: %s' % (thr, {k: float(v) for k, v in metrics.items()}))
+    if 'mesh_distance' in end_points:
+        from rfdnet_amd.iscnet.mesh_eval import METRIC_KEYS, class_means
+        md = end_points['mesh_distance']
+        for key in METRIC_KEYS:                                           # per ground-truth class, over the pairs with a number
+            print('mesh distance, %s per class: %s' % (key, class_means(md, md['pairs'][:, 2], key)))
     if 'completion_loss' in end_points:
         stats = end_points['iou_stats']
         print('completion loss: %.4f; mean voxel IoU over %d proposals: %s'

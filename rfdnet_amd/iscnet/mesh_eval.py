@@ -384,6 +384,74 @@ def scene_mesh_iou(meshes, proposal_ids, parsed_predictions, parsed_gts, gt_mesh
     return iou
 
 
+METRIC_KEYS = ('accuracy', 'completeness', 'chamfer_l1', 'chamfer_sq', 'precision', 'recall', 'fscore',
+               'normal_consistency', 'rms')
+
+
+@torch.no_grad()
+def scene_mesh_distance(meshes, proposal_ids, parsed_predictions, parsed_gts, gt_meshes, pairs, count=10000,
+                        thresholds=(0.05, 0.10), u_a=None, u_b=None, generator=None):
+    """The surface metrics of ONE scene's (proposal, ground truth) pairs -> mesh_distance.mesh_metrics' dict, one row per
+    pair, f64 on the device.  The generated meshes and the ground-truth meshes are placed exactly as scene_mesh_iou places
+    them (same arguments); pairs (P,2) or (P,3) integers: (proposal id, ground-truth row[, class]), the rows of
+    evaluation.proposal_to_gt for the scene.  The predictions are mesh_metrics' A, the ground truths its B: `precision`
+    is the share of the predicted surface near the true one, `recall` the share of the true surface that is covered.
+    A pair whose proposal has no mesh (not among proposal_ids, or generated empty), or whose ground truth is None or not
+    a labelled row, gets NaN in every metric.  u_a (K',count,3) / u_b (G',count,3): the randomness of the samples, one
+    slab per mesh in `meshes` / `gt_meshes` order."""
+    from .. import mesh_distance
+    corners = parsed_predictions['pred_corners_3d_upright_camera']
+    _lib.need_gpu(corners)
+    dev = corners.device
+    if corners.shape[0] != 1:
+        raise ValueError("mesh distance runs on one scene at a time, got a batch of %d" % corners.shape[0])
+    gt_corners = _lib.as_tensor(parsed_gts['gt_corners_3d_upright_camera'], dev, torch.float64)
+    rows_g = torch.nonzero(_lib.as_tensor(parsed_gts['box_label_mask'], dev, torch.float32)[0] == 1)[:, 0]
+    ids = proposal_ids.reshape(-1).to(dev) if torch.is_tensor(proposal_ids) else \
+        torch.as_tensor(np.asarray(proposal_ids).reshape(-1), device=dev)
+    if len(meshes) != ids.numel():
+        raise ValueError("meshes: %d meshes for %d proposal ids" % (len(meshes), ids.numel()))
+    if len(gt_meshes) != rows_g.numel():
+        raise ValueError("gt_meshes: %d meshes for %d ground-truth boxes" % (len(gt_meshes), rows_g.numel()))
+    pairs = np.asarray(pairs.cpu() if torch.is_tensor(pairs) else pairs, np.int64)
+    pairs = pairs.reshape(-1, pairs.shape[-1] if pairs.ndim > 1 else 2)[:, :2]
+    P, T = len(pairs), len(thresholds)
+    nan = lambda *shape: torch.full(shape, np.nan, dtype=torch.float64, device=dev)
+    out = {k: nan(P, T) if k in ('precision', 'recall', 'fscore') else nan(P) for k in METRIC_KEYS}
+    host = torch.cat([ids.long(), rows_g.long()]).cpu().numpy()                # the one copy: who has a mesh
+    ids_h, rows_h = host[:ids.numel()], host[ids.numel():]
+    mesh_of = {int(p): m for m, p in reversed(list(enumerate(ids_h)))}         # the first mesh of a proposal
+    gt_of = {int(g): j for j, g in enumerate(rows_h) if gt_meshes[j] is not None}
+    known = np.array([int(p) in mesh_of and int(g) in gt_of for p, g in pairs], bool)
+    if not known.any():
+        if T > mesh_distance.MAX_THRESHOLDS:
+            raise ValueError("%d thresholds: at most %d" % (T, mesh_distance.MAX_THRESHOLDS))
+        return out
+    local = np.array([[mesh_of[int(p)], gt_of[int(g)]] for p, g in pairs[known]], np.int64)
+    pred = scene_module.place_objects([_as_mesh(m, dev) for m in meshes], ids.view(1, -1, 1), parsed_predictions)
+    gt_cls = _lib.as_tensor(parsed_gts['sem_cls_label'], dev, torch.int32)[0][rows_g]
+    gt = scene_module.place_in_corners([_as_mesh(m, dev) for m in gt_meshes], gt_corners[0][rows_g], gt_cls)
+    got = mesh_distance.mesh_metrics(pred, gt, local, count, thresholds, u_a, u_b, generator)
+    at = torch.from_numpy(np.nonzero(known)[0]).to(dev)
+    for k in METRIC_KEYS:
+        out[k][at] = got[k]
+    return out
+
+
+def class_means(metrics, classes, key='chamfer_l1'):
+    """metrics: scene_mesh_distance's dict (or several, concatenated by the caller), classes (P) integers -> {class: the
+    mean of metrics[key] over the class's pairs that have a number}; what demo.py and tools/eval_sweep.py print."""
+    values = metrics[key].detach().cpu().numpy()
+    classes = np.asarray(classes.cpu() if torch.is_tensor(classes) else classes).reshape(-1)
+    out = {}
+    for c in np.unique(classes):
+        x = values[classes == c]
+        x = x[np.isfinite(x).reshape(len(x), -1).all(1)]
+        if len(x):
+            out[int(c)] = x.mean(0).tolist() if x.ndim > 1 else float(x.mean())
+    return out
+
+
 class MeshAPCalculator(APCalculator):
     """compute_metrics_w_mesh (ap_helper.py:84-122) on records with mesh flags (scene_records(mesh_iou=...)):
     compute_metrics() returns the box dict of APCalculator plus '<cls> Average Precision_mesh', 'mAP_mesh',

@@ -202,7 +202,8 @@ class ISCNet(nn.Module):
         return total_loss
 
     def evaluate(self, data, fit=True, ap_iou_thresh=(0.25, 0.5), timing=False, completion=False, completion_eps=None,
-                 losses=False, mesh=False, voxel_size=None):
+                 losses=False, mesh=False, voxel_size=None, mesh_distance=False, distance_samples=10000,
+                 distance_thresholds=(0.05, 0.10)):
         """The tail of the reference's `generate` in test mode (network.py:85-177): detection and completion with
         selection='nms', then (fit: True or 'autograd', or 'device' for the ragged loop of csrc/fit_pose.hip; False for
         none) the box refinement of fit_mesh_to_scan, then the evaluation records of the --
@@ -227,7 +228,13 @@ class ISCNet(nn.Module):
         == 1, None for a missing mesh -- in the ground-truth boxes, both sides are voxelised (voxel_size: 0.047) and the
         mesh IoU of every pair (mesh_eval.scene_mesh_iou, kept in end_points['mesh_iou'] (1,K,G)) is matched like the box
         IoU: the records carry 'tp_mesh' for mesh_eval.MeshAPCalculator.  A detection that takes part but has no mesh
-        has mesh IoU 0 with everything (the reference raises ValueError there)."""
+        has mesh IoU 0 with everything (the reference raises ValueError there).
+        mesh_distance=True (off by default: without it evaluate makes exactly the calls it made) adds the surface metrics
+        of every selected proposal against its ground truth (one scene; data['gt_meshes'] as for mesh=True): the pairs are
+        the rows of evaluation.proposal_to_gt, the meshes are placed as for the mesh IoU, and
+        end_points['mesh_distance'] = mesh_eval.scene_mesh_distance's dict (accuracy, completeness, chamfer_l1, chamfer_sq,
+        precision, recall, fscore, normal_consistency, rms; distance_samples points per mesh, distance_thresholds in
+        scan units) plus 'pairs' (P,3): proposal id, ground-truth row, ground-truth class."""
         from . import evaluation, fit as fit_module
         method = fit_module.fit_method(fit)
         captured = {}
@@ -254,6 +261,14 @@ class ISCNet(nn.Module):
             from . import mesh_eval
             mesh_iou = end_points['mesh_iou'] = mesh_eval.scene_mesh_iou(
                 meshes, ids, parsed, parsed_gts, data['gt_meshes'], voxel_size or mesh_eval.VOXEL_SIZE)
+        if mesh_distance:
+            from . import mesh_eval
+            pairs = captured['pairs'] if 'pairs' in captured else evaluation.proposal_to_gt(end_points, data, ids)
+            if pairs.shape[0] != 1:
+                raise ValueError("mesh distance runs on one scene at a time, got a batch of %d" % pairs.shape[0])
+            end_points['mesh_distance'] = dict(
+                mesh_eval.scene_mesh_distance(meshes, ids, parsed, parsed_gts, data['gt_meshes'], pairs[0],
+                                              distance_samples, distance_thresholds), pairs=pairs[0])
         records = evaluation.scene_records(eval_dict, parsed, parsed_gts, getattr(self.cfg, 'eval_overrides', None),
                                            ap_iou_thresh, timing=timing, mesh_iou=mesh_iou)
         return end_points, ids, meshes, records

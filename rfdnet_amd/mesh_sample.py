@@ -229,10 +229,11 @@ def voxelize_ray(vertices, faces, resolution, jitter=None, generator=None):
 
 
 @torch.no_grad()
-def sample_surface(vertices, faces, count, u=None, generator=None, return_normals=False, dtype=torch.float32):
+def sample_surface(vertices, faces, count, u=None, generator=None, return_normals=False, dtype=torch.float32, cum=None):
     """-> points (count,3) `dtype`, face_index (count,) i32 [, normals (count,3) `dtype`]: points uniform on the surface.
     u (count,3) f64 in [0,1) on the device is the randomness: u0 picks the face by area, u1 and u2 the point in it
-    (include/rfd_sample.h, rules S1 - S4); None: torch.rand from `generator`."""
+    (include/rfd_sample.h, rules S1 - S4); None: torch.rand from `generator`.  cum (F) f64 on the device: the inclusive
+    prefix of the areas to draw with (rule S2 leaves its summation order open); None: torch.cumsum of the areas."""
     count = int(count)
     if count < 0:
         raise ValueError("sample_surface: count = %d" % count)
@@ -245,9 +246,15 @@ def sample_surface(vertices, faces, count, u=None, generator=None, return_normal
     if count > 0:
         tri, _, _ = mesh_triangles(vertices, faces)
         F = int(tri.shape[0])
-        area = torch.empty(F, dtype=torch.float64, device=dev)
-        _lib.call("rfd_sample_face_areas", dev, F, tri.data_ptr(), area.data_ptr())
-        cum = torch.cumsum(area, 0)
+        if cum is None:
+            area = torch.empty(F, dtype=torch.float64, device=dev)
+            _lib.call("rfd_sample_face_areas", dev, F, tri.data_ptr(), area.data_ptr())
+            cum = torch.cumsum(area, 0)
+        else:
+            _lib.need_gpu(cum)
+            if cum.dtype != torch.float64 or tuple(cum.shape) != (F,):
+                raise ValueError("sample_surface: cum is (%d,) float64, got %s %s" % (F, cum.dtype, tuple(cum.shape)))
+            cum = cum.contiguous()
         check_total_area(float(cum[-1]) if F else 0., count)
         if u is None:
             u = torch.rand(count, 3, dtype=torch.float64, device=dev, generator=generator)

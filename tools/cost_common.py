@@ -1,5 +1,6 @@
 """What the *_cost.py tools share: the repository on sys.path, timing between HIP events, the "no GPU" exit, the JSON
-line, and the dented marching-cubes spheres that render_cost, decimate_cost, fuse_cost and sample_cost measure on.
+line, the dented marching-cubes spheres that render_cost, decimate_cost, fuse_cost and sample_cost measure on, and the
+scene of such spheres that render_cost and mesh_dist_cost share.
 Importing it is the tools' prologue; no *_cost.py imports another."""
 import json
 import os
@@ -82,3 +83,26 @@ def real_mesh():
     """one of those spheres as a mesh on the GPU -> vertices, faces"""
     from rfdnet_amd.iscnet.mcubes import marching_cubes_batch
     return marching_cubes_batch(object_grids(np.random.default_rng(5), 1), 0.)[0]
+
+
+def scene_inputs(n_obj, points=80000):
+    """the scene render_cost and mesh_dist_cost measure on: n_obj of those spheres as meshes in the synthetic scene's boxes (a
+    box used again: somewhere else) -> meshes, proposal ids, parsed predictions, scan"""
+    import types
+    from rfdnet_amd import synthetic
+    from rfdnet_amd.iscnet import box_util
+    from rfdnet_amd.iscnet.mcubes import marching_cubes_batch
+    pc, boxes, _ = synthetic.synthetic_scene(seed=100, n_raw=int(points * 1.5), n_points=points, return_boxes=True)
+    rng = np.random.default_rng(5)
+    again = np.arange(n_obj) >= len(boxes)                                       # a box used again: somewhere else
+    boxes = boxes[np.arange(n_obj) % len(boxes)].astype(np.float64)
+    offset, noise = placement_draws(rng, n_obj)
+    centre = boxes[:, :3] + again[:, None] * offset * (1., 1., 0.)
+    heading = boxes[:, 6] + noise
+    corners = box_util.box_corners_upright_camera(torch.from_numpy(centre), torch.from_numpy(boxes[:, 3:6]),
+                                                  torch.from_numpy(heading))[None].cuda()
+    grids = object_grids(rng, n_obj)
+    meshes = [types.SimpleNamespace(vertices=v, faces=f) for v, f in marching_cubes_batch(grids, 0.)]
+    parsed = {'pred_corners_3d_upright_camera': corners,
+              'pred_sem_cls': torch.from_numpy(rng.integers(0, 18, (1, n_obj))).cuda()}
+    return meshes, torch.arange(n_obj).view(1, n_obj, 1), parsed, torch.from_numpy(pc[None]).cuda()

@@ -19,6 +19,9 @@ seeded completion weights: the other figures of such a run are not comparable wi
 --mesh (synthetic scenes) adds mesh mAP: the ground-truth mesh of a box is a unit cube (12 faces) placed in the box,
 ISCNet.evaluate(mesh=True) voxelises it and the generated meshes, and "mAP_mesh@..." / "AR_mesh@..." join the line.  The
 timed legs then include the mesh stage ("scenes_per_s_with_eval").
+--mesh_distance (synthetic scenes, one process) adds "mesh_distance": the per-class means of the Chamfer distance, the
+F-score and the normal consistency of every selected proposal's mesh against its ground truth's unit cube
+(ISCNet.evaluate(mesh_distance=True)), from a pass of its own after the timed legs.
 With --gpus M the scenes are dealt round robin to M processes (sharding.launch_local_ranks) and the records meet in
 one all_gather (sharding.gather_records); throughput is all scenes over the slowest rank.
 """
@@ -83,7 +86,7 @@ def load_scene(args, i, cfg, files):
                 data[k] = np.zeros((1, max_obj) + a.shape[1:], np.float32)
                 data[k][0, :len(boxes)] = a
     out = {k: torch.from_numpy(v).cuda() for k, v in data.items()}
-    if getattr(args, 'mesh', False):
+    if getattr(args, 'mesh', False) or getattr(args, 'mesh_distance', False):
         out['gt_meshes'] = [(CUBE_VERTICES, CUBE_FACES)] * int((data['box_label_mask'][0] == 1).sum())
     return out
 
@@ -106,8 +109,13 @@ def main():
                     help="synthetic scenes, --gpus 1: also report the completion loss and the voxel IoU")
     ap.add_argument("--mesh", action="store_true",
                     help="synthetic scenes: also report mesh mAP / AR against unit-cube ground-truth meshes")
+    ap.add_argument("--mesh_distance", action="store_true",
+                    help="synthetic scenes, --gpus 1: also report the surface metrics of every selected proposal against "
+                         "its unit-cube ground-truth mesh (per-class means of the Chamfer distance and the F-score)")
     ap.add_argument("--out", type=str, default=os.path.join(ROOT, "profiles", "eval_stage.json"))
     args = ap.parse_args()
+    if args.mesh_distance and (args.gt or args.gpus > 1):
+        ap.error("--mesh_distance runs on synthetic scenes in one process")
     if args.mesh and args.gt:
         ap.error("--mesh runs on synthetic scenes (their ground-truth meshes are unit cubes)")
     if args.completion and (args.gt or args.gpus > 1):
@@ -187,6 +195,19 @@ def main():
             ious += [] if ep['iou_stats'] is None else list(ep['iou_stats']['iou'])
         completion = {"loss": float(np.mean(losses)) if losses else None, "proposals": len(ious),
                       "voxel_iou": float(np.nanmean(ious)) if ious else None}
+    distance = None
+    if args.mesh_distance:
+        from rfdnet_amd.iscnet.mesh_eval import class_means
+        rows = {'chamfer_l1': [], 'fscore': [], 'normal_consistency': [], 'cls': []}
+        for i in mine:
+            md = net.evaluate(load_scene(args, i, cfg, files), fit=fit, ap_iou_thresh=thr, mesh_distance=True)[0]['mesh_distance']
+            for k in ('chamfer_l1', 'fscore', 'normal_consistency'):
+                rows[k].append(md[k])
+            rows['cls'].append(md['pairs'][:, 2])
+        if rows['cls']:
+            cat = {k: torch.cat(v) for k, v in rows.items()}
+            distance = {"pairs": int(cat['cls'].numel()), "thresholds": [0.05, 0.10],
+                        "per_class": {k: class_means(cat, cat['cls'], k) for k in ('chamfer_l1', 'fscore', 'normal_consistency')}}
     # per rank: scenes, seconds without / with the evaluation, summed stage milliseconds
     mine_t = torch.tensor([len(mine), t_off, t_on, sum(stage_ms)], dtype=torch.float64, device="cuda")
     if dist is not None:
@@ -221,6 +242,8 @@ def main():
                          "mAP_mesh@0.5": num(m50)['mAP_mesh'], "AR_mesh@0.5": num(m50)['AR_mesh']})
         if completion is not None:
             line["completion"] = completion
+        if distance is not None:
+            line["mesh_distance"] = distance
         text = json.dumps(line)
         print(text)
         if args.out:

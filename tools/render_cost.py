@@ -11,32 +11,9 @@ the scene's own reconstruction time from the benchmark records profiles/r06_benc
 import argparse
 import json
 import os
-import types
-
-import numpy as np
 import torch
 
-from cost_common import ROOT, emit, need_gpu_or_exit, object_grids, placement_draws, timed
-
-
-def scene_inputs(n_obj, points=80000):
-    from rfdnet_amd import synthetic
-    from rfdnet_amd.iscnet import box_util
-    from rfdnet_amd.iscnet.mcubes import marching_cubes_batch
-    pc, boxes, _ = synthetic.synthetic_scene(seed=100, n_raw=int(points * 1.5), n_points=points, return_boxes=True)
-    rng = np.random.default_rng(5)
-    again = np.arange(n_obj) >= len(boxes)                                       # a box used again: somewhere else
-    boxes = boxes[np.arange(n_obj) % len(boxes)].astype(np.float64)
-    offset, noise = placement_draws(rng, n_obj)
-    centre = boxes[:, :3] + again[:, None] * offset * (1., 1., 0.)
-    heading = boxes[:, 6] + noise
-    corners = box_util.box_corners_upright_camera(torch.from_numpy(centre), torch.from_numpy(boxes[:, 3:6]),
-                                                  torch.from_numpy(heading))[None].cuda()
-    grids = object_grids(rng, n_obj)
-    meshes = [types.SimpleNamespace(vertices=v, faces=f) for v, f in marching_cubes_batch(grids, 0.)]
-    parsed = {'pred_corners_3d_upright_camera': corners,
-              'pred_sem_cls': torch.from_numpy(rng.integers(0, 18, (1, n_obj))).cuda()}
-    return meshes, torch.arange(n_obj).view(1, n_obj, 1), parsed, torch.from_numpy(pc[None]).cuda()
+from cost_common import ROOT, emit, need_gpu_or_exit, scene_inputs, timed
 
 
 def measure(label, n_obj, record, reps, warmup):
