@@ -7,6 +7,7 @@ write the reference's output files.
   python demo.py --synthetic 10 --out out/synth --upsampling_steps 1
   python demo.py --synthetic 10 --out out/synth --with_normals     (PLYs with per-vertex nx ny nz)
   python demo.py --synthetic 10 --out out/synth --refinement_step 30   (meshes refined against the occupancy field)
+  python demo.py --synthetic 10 --out out/synth --keep_components largest   (floaters dropped: the largest component stays)
   python demo.py --synthetic 10 --out out/synth --decimate_cells 16    (meshes thinned by vertex clustering, 16^3 cells)
   python demo.py --synthetic 10 --out out/synth --simplify_nfaces 500   (meshes collapsed to 500 faces each, watertight)
   python demo.py --synthetic 10 --out out/synth --render --post_processing  (scene_objects.ply and pred.png as well)
@@ -19,6 +20,16 @@ import time
 
 import numpy as np
 import torch
+
+
+def keep_components_arg(text):
+    """--keep_components: 'largest' or a fraction in [0, 1]"""
+    if text == 'largest':
+        return text
+    t = float(text)
+    if not 0.0 <= t <= 1.0:
+        raise argparse.ArgumentTypeError("largest, or a fraction in [0, 1]")
+    return t
 
 
 def build_parser():
@@ -70,6 +81,11 @@ def build_parser():
                     help="simplify every mesh to at most N faces by quadric edge collapse on the device, after "
                          "--decimate_cells and before normals and refinement (Generator3D.set_simplification; "
                          "generation.simplify_faces, 0 = off)")
+    ap.add_argument("--keep_components", type=keep_components_arg, default=None, metavar="largest|T",
+                    help="drop the floaters of every mesh right after marching cubes, before --decimate_cells and "
+                         "--simplify_nfaces: keep the largest connected component alone, or every component with at "
+                         "least the fraction T of the largest's area (Generator3D.set_components; "
+                         "generation.keep_components, 0 = off)")
     ap.add_argument("--render", action="store_true",
                     help="place every mesh in its box (iscnet.scene.place_objects), render scan and meshes on the device "
                          "and write scene_objects.ply and pred.png beside the other files (demo.py:329-377; needs "
@@ -90,7 +106,7 @@ def main():
 
     gen = {k: v for k, v in (('resolution_0', args.resolution_0), ('upsampling_steps', args.upsampling_steps),
                              ('refinement_step', args.refinement_step), ('decimate_cells', args.decimate_cells),
-                             ('simplify_faces', args.simplify_nfaces))
+                             ('simplify_faces', args.simplify_nfaces), ('keep_components', args.keep_components))
            if v is not None}
     if args.with_normals:
         gen['with_normals'] = True

@@ -78,6 +78,8 @@ class Generator3D(object):
         self.refine_eps_source, self.refine_seed = 'numpy', None       # set_refinement()
         self.decimate_cells = 0         # set_decimation()
         self.simplify_faces = 0         # set_simplification()
+        self.components = None          # set_components(): (keep, measure, drop_cavities)
+        self.last_components = None     # {'found': [...], 'kept': [...]} of the last extract_meshes(); None when off
         self._round0_cache = _lib.ArtefactCache(64)     # made here: the worker views of one network share it
 
     def set_refinement(self, steps, eps_source='numpy', seed=None):
@@ -105,6 +107,22 @@ class Generator3D(object):
         if cells < 0:
             raise ValueError("decimation cells must be >= 0")
         self.decimate_cells = cells
+        return self
+
+    def set_components(self, keep, measure='area', drop_cavities=False):
+        """Drop the floaters of every extracted mesh (components.py): keep='largest' keeps the largest connected component
+        of every mesh alone, a fraction t in (0, 1] every component whose `measure` ('faces', 'area' or 'abs_volume') is at
+        least t times the largest's; drop_cavities also drops inside-out inner shells.  It runs directly after marching
+        cubes, BEFORE set_decimation() / set_simplification(), so their budgets go to the object; normals, refinement,
+        last_buffers and the Mesh list are those of the filtered meshes, and last_components holds what was found and
+        kept.  None / 0 / False = off (the default).  The reference has no such step."""
+        from .components import parse_keep, parse_measure
+        if keep is None or keep is False or (not isinstance(keep, str) and keep == 0):
+            self.components = None
+            return self
+        parse_keep(keep)
+        parse_measure(measure)
+        self.components = (keep if isinstance(keep, str) else float(keep), measure, bool(drop_cavities))
         return self
 
     def set_simplification(self, n_faces):
@@ -276,7 +294,7 @@ class Generator3D(object):
         (Generator3D.estimate_normals), one launch for all meshes; with set_refinement(), the refinement of all meshes
         (refine_meshes) -- after the normals, which belong to the unrefined vertices as in the reference (generator.py:173-195).
         With set_decimation() / set_simplification() the meshes are thinned first: normals, refinement, last_buffers and the
-        Mesh list are those of the thinned meshes."""
+        Mesh list are those of the thinned meshes.  With set_components() the floaters are dropped before all of that."""
         from .mcubes import marching_cubes_batch
         thr = self.logit_threshold()
         n = grids.shape[1]
@@ -290,6 +308,12 @@ class Generator3D(object):
         a = box_size / (n - 1)
         v, f, vend, tend = marching_cubes_batch(grids, thr, pad_value=-1e6, return_flat=True,
                                                 affine=(a, -1.5 * a - 0.5 * box_size))
+        self.last_components = None
+        if self.components is not None:
+            from .components import keep_components
+            keep, measure, drop_cavities = self.components
+            v, f, vend, tend, self.last_components = keep_components(v, f, vend, tend, keep=keep, measure=measure,
+                                                                     drop_cavities=drop_cavities, return_info=True)
         if self.decimate_cells:
             from .decimate import decimate_meshes
             K = len(vend) - 1

@@ -46,6 +46,8 @@ class ONet(nn.Module):
                 self.generator.set_decimation(gen['decimate_cells'])
             if gen.get('simplify_faces'):       # nor is this one (the reference's simplify_nfaces still raises)
                 self.generator.set_simplification(gen['simplify_faces'])
+            if gen.get('keep_components'):      # nor this one: 'largest' or a fraction (Generator3D.set_components)
+                self.generator.set_components(gen['keep_components'])
 
     def enable_latent_encoder(self):
         """Attach the latent encoder (z_dim > 0; occupancy_net.py:40-43) in front of the decoder, so that state_dict()

@@ -2,11 +2,13 @@
 utils/shapenet/1_fuse_shapenetv2.py, and with --decimate_cells the place of its 3_simplify_fusion.py).
 
     python tools/make_watertight.py IN.{off,obj,ply} OUT.off [--resolution 256] [--views 200] [--image_size 640]
-                                    [--decimate_cells N]
+                                    [--keep_components largest|T [--drop_cavities]] [--decimate_cells N]
 
 The focal length is the image size, as in the reference (640 at 640 x 640).  --decimate_cells N thins the result with the
-device decimation (rfdnet_amd.iscnet.decimate) on a grid of N^3 cells over the mesh's bounding cube.  Prints one JSON
-line: the counts of what was read and what was written."""
+device decimation (rfdnet_amd.iscnet.decimate) on a grid of N^3 cells over the mesh's bounding cube.  --keep_components
+drops the fused mesh's floaters before that (rfdnet_amd.iscnet.components): `largest` keeps the largest connected
+component alone, a fraction T every component with at least T times the largest's area; --drop_cavities also drops
+inside-out inner shells.  Prints one JSON line: the counts of what was read and what was written."""
 import argparse
 import json
 import os
@@ -19,7 +21,16 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 
-def main():
+def keep_components_arg(text):
+    if text == 'largest':
+        return text
+    t = float(text)
+    if not 0.0 <= t <= 1.0:
+        raise argparse.ArgumentTypeError("largest, or a fraction in [0, 1]")
+    return t
+
+
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("input")
     ap.add_argument("output")
@@ -27,7 +38,13 @@ def main():
     ap.add_argument("--views", type=int, default=200)
     ap.add_argument("--image_size", type=int, default=640)
     ap.add_argument("--decimate_cells", type=int, default=0)
-    args = ap.parse_args()
+    ap.add_argument("--keep_components", type=keep_components_arg, default=None, metavar="largest|T")
+    ap.add_argument("--drop_cavities", action="store_true")
+    return ap
+
+
+def main():
+    args = build_parser().parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("make_watertight runs on a GPU: none is visible")
     from rfdnet_amd import io
@@ -42,6 +59,13 @@ def main():
                         n_views=args.views, image_size=args.image_size, focal=float(args.image_size))
     result = {"tool": "make_watertight", "input": {"vertices": int(len(v)), "faces": int(len(f))},
               "watertight": {"vertices": int(vt.shape[0]), "faces": int(ft.shape[0])}}
+    if (args.keep_components is not None or args.drop_cavities) and ft.shape[0]:
+        from rfdnet_amd.iscnet.components import keep_components
+        keep = 0.0 if args.keep_components is None else args.keep_components      # --drop_cavities alone: the rest stays
+        vt, ft, _, _, info = keep_components(vt, ft, [0, vt.shape[0]], [0, ft.shape[0]], keep=keep,
+                                             drop_cavities=args.drop_cavities, return_info=True)
+        result["components"] = {"found": info["found"][0], "kept": info["kept"][0]}
+        result["kept"] = {"vertices": int(vt.shape[0]), "faces": int(ft.shape[0])}
     if args.decimate_cells and ft.shape[0]:
         from rfdnet_amd.iscnet.decimate import decimate_meshes
         lo, hi = vt.amin(0).cpu().numpy(), vt.amax(0).cpu().numpy()
