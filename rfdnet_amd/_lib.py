@@ -18,7 +18,7 @@ _sz = C.c_size_t
 _d = C.c_double
 
 # name -> (restype, argtypes[, OPTIONAL]): exactly the prototypes of include/rfd_pointnet2.h / rfd_occ.h /
-# rfd_chamfer.h / rfd_eval.h / rfd_latent.h / rfd_loss.h / rfd_fit.h / rfd_render.h / rfd_decimate.h / rfd_simplify.h / rfd_fuse.h / rfd_sample.h / rfd_labels.h / rfd_mesh_eval.h / rfd_objgrid.h / rfd_mesh_dist.h / rfd_components.h.  OPTIONAL marks the test hooks, which a deployment build (RFD_NO_TEST_HOOKS=1, build.py)
+# rfd_chamfer.h / rfd_eval.h / rfd_latent.h / rfd_loss.h / rfd_fit.h / rfd_render.h / rfd_decimate.h / rfd_simplify.h / rfd_fuse.h / rfd_sample.h / rfd_labels.h / rfd_mesh_eval.h / rfd_objgrid.h / rfd_mesh_dist.h / rfd_components.h / rfd_knn.h.  OPTIONAL marks the test hooks, which a deployment build (RFD_NO_TEST_HOOKS=1, build.py)
 # leaves out.
 OPTIONAL = "optional"
 ABI = {
@@ -150,6 +150,10 @@ ABI = {
     "rfd_components_mark": (_i, [_i, _i, _i, _f, _f, _f, _f, _f, _f]),
     "rfd_components_compact_faces": (_i, [_i, _i, _i, _f, _f, _f, _f, _f, _f, _f, _f]),
     "rfd_components_gather_vertices": (_i, [_i, _i, _i, _f, _f, _f, _f, _f]),
+    "rfd_knn_points": (_i, [_i, _i, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f]),
+    "rfd_knn_cells": (_i, [_i, _f, _i, _f, _f, _i, _f, _f, _f]),
+    "rfd_knn_query": (_i, [_i, _f, _f, _i, _d, _f, _i, _i, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _i, _f, _f, _f, _f]),
+    "rfd_knn_sums": (_i, [_i, _i, _i, _f, _f, _f, _f, _i, _i, _f, _f, _f, _i, _f, _f, _f, _f]),
     "rfd_last_error_string": (C.c_char_p, []),
     "rfd_build_arch": (C.c_char_p, []),
     "rfd_device_status": (_i, []),

@@ -8,7 +8,8 @@
   read_mesh           "a mesh file" of the mesh tools: .off, .obj or .ply -> float64 vertices, int32 triangles
   write_binvox        `#binvox 1` voxel grids as the reference's external/binvox_rw.py writes them
   read_binvox         (axis order xyz, run-length pairs); write_points_npz / write_pointcloud_npz:
-                      points.npz and pointcloud.npz of utils/shapenet/2_sample_mesh.py
+                      points.npz and pointcloud.npz of utils/shapenet/2_sample_mesh.py;
+                      read_pointcloud_npz reads the latter back
   load_demo_data      demo.py:24-48: vertices -> [xyz | height] -> random_sampling
                       (utils/pc_util.py:35-47) -> (1, N, 4) float32 tensor
   write_mesh_ply      `proposal_%d_mesh.ply` as trimesh exports it (binary
@@ -169,6 +170,28 @@ def write_pointcloud_npz(path, points, normals, loc, scale, float16=False, packb
     nothing boolean in it: packbits is accepted for symmetry with write_points_npz and changes nothing."""
     points, loc, scale = _npz_arrays(points, loc, scale, float16)
     np.savez(path, points=points, normals=np.asarray(normals).astype(points.dtype), loc=loc, scale=scale)
+
+
+def read_pointcloud_npz(path, original_frame=False):
+    """The inverse of write_pointcloud_npz -> points (n,3), normals (n,3), loc (3,) f64, scale (float).  Points and normals
+    come back as float32 (a float16 file is upcast, which is exact).  The file's points are in the unit cube of
+    tools/sample_mesh.py, p = (x - loc) / scale; original_frame=True returns x = p scale + loc in float64 instead (the
+    normals are directions and stay)."""
+    with np.load(path) as z:
+        missing = [k for k in ("points", "normals") if k not in z.files]
+        if missing:
+            raise ValueError("%s: no %s (a pointcloud.npz holds points, normals, loc, scale)" % (path, ", ".join(missing)))
+        points, normals = z["points"], z["normals"]
+        loc = np.asarray(z["loc"], np.float64).reshape(3) if "loc" in z.files else np.zeros(3)
+        scale = float(z["scale"]) if "scale" in z.files else 1.
+    if points.ndim != 2 or points.shape[1] != 3 or normals.shape != points.shape:
+        raise ValueError("%s: points %s and normals %s are not two (n,3) arrays" % (path, points.shape, normals.shape))
+    if points.dtype not in (np.float16, np.float32) or normals.dtype not in (np.float16, np.float32):
+        raise ValueError("%s: points are %s, normals %s: float16 or float32 expected" % (path, points.dtype, normals.dtype))
+    points, normals = points.astype(np.float32), normals.astype(np.float32)
+    if original_frame:
+        points = points.astype(np.float64) * scale + loc
+    return points, normals, loc, scale
 
 
 def random_sampling(pc, num_sample, rng, replace=None):
